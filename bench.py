@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: sampled images/sec of the DGM denoising hot path (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], README inference config at 128x128): CFG Unet dim=64,
@@ -504,7 +504,14 @@ def main():
     ap.add_argument('--cpu-probe', type=int, default=0, help='internal: the child-process mode of cpu_baseline (see cpu_probe)')
     ap.add_argument('--device', default='cuda', choices=['cuda', 'cpu'],
                     help="'cpu' is the test-only plumbing mode of tests/test_distributed_cpu.py (raises elsewhere)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (rank 0\'s gathered records: '
+                         'imgs as float32, homos as float64) to DIR/<name>.npy, at most 64 MB in all (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.workload != 'sample' or args.device != 'cuda'):
+        ap.error('--dump-outputs covers the sampling workload on the GPU only')
     if args.cpu_probe:
         return cpu_probe(args)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -583,6 +590,8 @@ def main():
     elapsed_local = time.perf_counter() - t0             # this rank's own finish line (before it waits for the others)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)             # (outside the timed region, before the untimed extra steps)
     # ---- phases (N-rank diagnosis; all of it OUTSIDE the timed region): the SMU's averages right after the loop, then one
     # instrumented step with the local work (sample + record) and the gather timed apart, a barrier between them so that the
     # gather's time is the transport, not the wait for the slowest rank
@@ -722,6 +731,31 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the gathered records of the last timed step, as a caller of step() receives them, for comparing two
+    builds output for output.  DIR/imgs.npy = the uint8 image pairs as float32 (N, 6, S, S), DIR/homos.npy = the float64
+    homographies (N, 3, 3).  When the images exceed the 64 MB budget, a fixed sample of whole rows (numpy seed 0, sorted) is
+    written instead, and DIR/imgs_rows.npy (float64) holds the row indices it took."""
+    import numpy as np
+    imgs, homos = records
+    imgs = imgs.cpu().numpy().astype(np.float32)
+    homos = homos.cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    n = imgs.shape[0]
+    fit = max(1, (DUMP_LIMIT_BYTES - homos.nbytes - 8 * n) // max(imgs[:1].nbytes, 1))
+    if fit < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=fit, replace=False))
+        imgs = imgs[rows]
+        np.save(os.path.join(out_dir, 'imgs_rows.npy'), rows.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, 'imgs_rows.npy')):
+        os.remove(os.path.join(out_dir, 'imgs_rows.npy'))     # (left by an earlier, larger run into the same DIR)
+    np.save(os.path.join(out_dir, 'imgs.npy'), imgs)
+    np.save(os.path.join(out_dir, 'homos.npy'), homos)
 
 
 def measure_traffic(timeout=240):

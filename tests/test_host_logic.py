@@ -286,3 +286,33 @@ def test_training_refuses_learned_sinusoidal_models():
         m = cfg.Unet(dim=8, dim_mults=(1, 2), channels=6, num_classes=1, **kw)
         with pytest.raises(NotImplementedError, match='learned_sinusoidal_cond'):
             train.UnetTrain(m)
+
+
+def test_bench_dump_outputs_writes_the_records_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's records as DIR/imgs.npy (float32) + DIR/homos.npy (float64); over the
+    budget, a fixed seeded sample of whole image rows plus their indices (DIR/imgs_rows.npy), the same on every call"""
+    import importlib.util
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    imgs = torch.randint(0, 256, (10, 6, 8, 8), generator=g, dtype=torch.uint8)
+    homos = torch.randn(10, 3, 3, generator=g, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'all'), (imgs, homos))
+    a = np.load(str(tmp_path / 'all' / 'imgs.npy'))
+    h = np.load(str(tmp_path / 'all' / 'homos.npy'))
+    assert a.dtype == np.float32 and np.array_equal(a, imgs.numpy().astype(np.float32))
+    assert h.dtype == np.float64 and np.array_equal(h, homos.numpy())
+    assert sorted(os.listdir(str(tmp_path / 'all'))) == ['homos.npy', 'imgs.npy']
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4 * 6 * 8 * 8 * 4 + homos.numel() * 8 + 8 * 10)    # room for 4 rows
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), (imgs, homos))
+    rows = np.load(str(tmp_path / 's1' / 'imgs_rows.npy'))
+    assert rows.dtype == np.float64 and len(rows) == 4 and list(rows) == sorted(set(rows))
+    a1, a2 = np.load(str(tmp_path / 's1' / 'imgs.npy')), np.load(str(tmp_path / 's2' / 'imgs.npy'))
+    assert np.array_equal(a1, a2) and np.array_equal(rows, np.load(str(tmp_path / 's2' / 'imgs_rows.npy')))
+    assert np.array_equal(a1, imgs.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert sum(os.path.getsize(str(tmp_path / 's1' / f)) for f in os.listdir(str(tmp_path / 's1'))) < 4096 + bench.DUMP_LIMIT_BYTES
