@@ -7,38 +7,13 @@
 // memory and is advanced by the launch itself (the last workgroup to finish), so a captured denoise step replays
 // with fresh noise and no host bookkeeping.
 #include "common.h"
+#include "philox.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-// (0, 1]-open-at-zero uniform of a 32-bit word, as cuRAND / torch's CUDA generator place it: x * 2^-32 + 2^-33
-__device__ __forceinline__ float u01(uint32_t x) { return (float)x * 2.3283064365386963e-10f + 1.1641532182693481e-10f; }
-
-// Box-Muller: two words -> two standard normals
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
-  const float r = sqrtf(-2.0f * logf(u01(a)));
-  float s, c;
-  sincospif(2.0f * u01(b), &s, &c);
-  n0 = r * c;
-  n1 = r * s;
-}
+using namespace dmh_philox;
 
 // grid: (blocks per sample, B).  kind 0: N(0,1); 1: uniform; 2: the raw words (bit patterns stored in the floats)
 __global__ __launch_bounds__(256) void rng_indexed_kernel(float* __restrict__ out, int64_t per, const int64_t* __restrict__ ids,

@@ -2,6 +2,7 @@
 // assembly, final 1x1 conv back to NCHW, classifier-free-guidance blend + x0 clamp + DDIM /
 // DDPM update, uint8 export.  Mirrors the reference's fp32 op order (no FMA contraction).
 #include "common.h"
+#include "philox.h"
 
 #pragma clang fp contract(off)
 
@@ -226,6 +227,122 @@ __global__ __launch_bounds__(256) void sampler_step_dev_kernel(const DmhStep* __
   }
 }
 
+// dmh_sampler_step_ddp_dev: the replayed step of the unconditional loop (DDP:647-729) in one pass — the step of
+// sampler_step_dev_kernel (same operations, same order, model_null absent), its noise drawn here from the sample-indexed
+// generator (the values rng_indexed_kernel would have stored; never stored) or read from `noise`, and the next step's network
+// input written as dmh_assemble_input writes it.  One thread per P pixels of a row and every channel: P = 4 when HW % 4 == 0,
+// where the 4 pixels of one channel are exactly one Philox counter quad; P = 1 otherwise (a thread then draws its element's
+// quad and keeps one lane).  The channel loop is not unrolled and no array is indexed by a runtime value (no scratch).
+template <int P>
+__global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __restrict__ sp, const int32_t* __restrict__ cursor,
+                                                               const int32_t* __restrict__ draws, const float* __restrict__ mc,
+                                                               float* img, const float* __restrict__ noise,
+                                                               const int64_t* __restrict__ ids, unsigned long long* state,
+                                                               float* __restrict__ x_start, float* __restrict__ xin, int C, int HW,
+                                                               int cpad, int sc, int64_t ngroups) {
+  const DmhStep s = *sp;
+  const bool drawn = draws[*cursor] != 0;   // eager runs this entry with noise (else: no draw, no advance)
+  const bool keyed = ids != nullptr && drawn;
+  unsigned long long seed = 0, draw = 0;
+  if (keyed) seed = state[0], draw = state[1];
+  const int G = HW / P;
+  const int cin = sc ? 2 * C : C;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256) {
+    const int64_t b = g / G;
+    const int p0 = (int)(g - b * G) * P;
+    const unsigned long long sid = keyed ? (unsigned long long)ids[b] : 0ull;
+    float* xo = xin ? xin + ((size_t)b * HW + p0) * cpad : nullptr;
+    for (int c = 0; c < C; ++c) {
+      const size_t base = ((size_t)b * C + c) * HW + p0;
+      float mo[P], xt[P], nz[P];
+      if constexpr (P == 4) {
+        const float4 m4 = ld4(mc + base), x4 = ld4(img + base);
+        mo[0] = m4.x, mo[1] = m4.y, mo[2] = m4.z, mo[3] = m4.w;
+        xt[0] = x4.x, xt[1] = x4.y, xt[2] = x4.z, xt[3] = x4.w;
+      } else {
+        mo[0] = mc[base];
+        xt[0] = img[base];
+      }
+      if (keyed) {
+        const int64_t e = (int64_t)c * HW + p0;   // element of the row: counter quad e / 4, lane e % 4
+        float v[4];
+        dmh_philox::normal4(seed, draw, sid, (uint64_t)(e >> 2), v);
+        if constexpr (P == 4) {
+#pragma unroll
+          for (int j = 0; j < P; ++j) nz[j] = v[j];
+        } else {
+          const int l = (int)(e & 3);
+          nz[0] = l == 0 ? v[0] : (l == 1 ? v[1] : (l == 2 ? v[2] : v[3]));
+        }
+      } else if (drawn && noise) {
+        if constexpr (P == 4) {
+          const float4 n4 = ld4(noise + base);
+          nz[0] = n4.x, nz[1] = n4.y, nz[2] = n4.z, nz[3] = n4.w;
+        } else {
+          nz[0] = noise[base];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < P; ++j) nz[j] = __builtin_nanf("");   // (a drawing entry without a noise source: NaN, as _dev)
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const float m = mo[j], x = xt[j];
+        float x0, pn;
+        if (s.objective == 0) {
+          pn = m;
+          x0 = s.sqrt_recip_ac * x - s.sqrt_recipm1_ac * pn;
+          if (s.clip) x0 = clamp_pm1(x0);
+        } else if (s.objective == 1) {
+          x0 = m;
+          if (s.clip) x0 = clamp_pm1(x0);
+          pn = (s.sqrt_recip_ac * x - x0) / s.sqrt_recipm1_ac;
+        } else {
+          x0 = s.sqrt_ac * x - s.sqrt_1m_ac * m;
+          if (s.clip) x0 = clamp_pm1(x0);
+          pn = (s.sqrt_recip_ac * x - x0) / s.sqrt_recipm1_ac;
+        }
+        float o;
+        if (s.mode == 0) {
+          o = x0 * s.c0 + s.c1 * pn + s.c2 * nz[j];
+        } else if (s.mode == 1) {
+          o = x0;
+        } else {
+          o = s.c0 * x0 + s.c1 * x;
+          if (drawn) o = o + s.c2 * nz[j];
+        }
+        img[base + j] = o;
+        if (x_start) x_start[base + j] = x0;
+        if (xo) {   // cat((x_start, img)) with self-conditioning, img alone without (DDP:411), NHWC
+          if (sc) {
+            xo[(size_t)j * cpad + c] = x0;
+            xo[(size_t)j * cpad + C + c] = o;
+          } else {
+            xo[(size_t)j * cpad + c] = o;
+          }
+        }
+      }
+    }
+    if (xo) {
+      for (int k = cin; k < cpad; ++k)
+#pragma unroll
+        for (int j = 0; j < P; ++j) xo[(size_t)j * cpad + k] = 0.f;
+    }
+  }
+  // the draw index advances once per drawing launch, as rng_indexed_kernel advances it: every workgroup has read it before
+  // it takes a ticket; the last to arrive advances it and puts the ticket counter back
+  if (keyed) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned long long t = atomicAdd(&state[2], 1ull);
+      if (t == (unsigned long long)gridDim.x - 1) {
+        state[2] = 0;
+        state[1] = draw + 1;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void sampler_seek_kernel(int32_t* cursor, int k, const DmhStep* __restrict__ table,
                                                           const int64_t* __restrict__ times, int S, DmhStep* cur,
                                                           int64_t* tcond, int B) {
@@ -399,6 +516,37 @@ extern "C" int dmh_sampler_step_dev(const DmhStep* cur_dev, const float* model_c
   hipLaunchKernelGGL(sampler_step_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, cur_dev, model_cond,
                      model_null, x, noise, img_out, x_start, pred_noise, n, keep, per_row);
   DMH_CHECK_LAUNCH("dmh_sampler_step_dev");
+  return DMH_OK;
+}
+
+extern "C" int dmh_sampler_step_ddp_dev(const DmhStep* cur_dev, const int32_t* cursor, const int32_t* draws,
+                                        const float* model_out, float* img, const float* noise, const int64_t* sample_ids,
+                                        uint64_t* state, float* x_start, float* xin_next, int B, int C, int HW, int cpad,
+                                        int self_cond, void* stream) {
+  DMH_REQUIRE(cur_dev && cursor && draws && model_out && img && B > 0 && C > 0 && HW > 0 && (self_cond == 0 || self_cond == 1),
+              "dmh_sampler_step_ddp_dev: bad arguments");
+  DMH_REQUIRE(!sample_ids == !state, "dmh_sampler_step_ddp_dev: sample_ids and state go together (the keyed generator)");
+  DMH_REQUIRE(!(noise && sample_ids), "dmh_sampler_step_ddp_dev: two noise sources (noise and the keyed generator)");
+  const int cin = self_cond ? 2 * C : C;
+  DMH_REQUIRE(C <= 4096 && cpad % 4 == 0 && cpad >= cin && cpad <= 16384,
+              "dmh_sampler_step_ddp_dev: cpad=%d must be a multiple of 4 >= %d input channels", cpad, cin);
+  DMH_REQUIRE((int64_t)B * HW < ((int64_t)1 << 31) && (int64_t)C * HW < ((int64_t)1 << 34),
+              "dmh_sampler_step_ddp_dev: B=%d x HW=%d pixels (limit 2^31), C=%d x HW elements per row (limit 2^34)", B, HW, C);
+  // (every product below now fits int64: B*HW < 2^31, C and cpad < 2^15)
+  const bool quad = HW % 4 == 0 &&
+                    (((uintptr_t)model_out | (uintptr_t)img | (uintptr_t)noise | (uintptr_t)x_start) & 15) == 0;
+  const int64_t ngroups = (int64_t)B * HW / (quad ? 4 : 1);
+  // a drawing launch ends with one returning atomic per workgroup (the arrival ticket): at most 1024 workgroups, each looping
+  unsigned grid = grid_for(ngroups);
+  grid = grid < 1024 ? grid : 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (quad)
+    hipLaunchKernelGGL(sampler_step_ddp_kernel<4>, dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img, noise,
+                       sample_ids, (unsigned long long*)state, x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+  else
+    hipLaunchKernelGGL(sampler_step_ddp_kernel<1>, dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img, noise,
+                       sample_ids, (unsigned long long*)state, x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+  DMH_CHECK_LAUNCH("dmh_sampler_step_ddp_dev");
   return DMH_OK;
 }
 

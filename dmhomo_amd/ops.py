@@ -371,13 +371,16 @@ def ss_gather(T, Ct, bias, cursor, classes, keep, out=None):
 
 
 # ------------------------------------------------------------------ sampler glue
-def assemble_input(a, b=None, m=None, reps=1, cpad=None):
-    """(B,Ca,H,W) [+ (B,Cb,H,W) * (B,1,H,W)] NCHW -> NHWC (reps*B, H, W, cpad), zero padded."""
+def assemble_input(a, b=None, m=None, reps=1, cpad=None, out=None):
+    """(B,Ca,H,W) [+ (B,Cb,H,W) * (B,1,H,W)] NCHW -> NHWC (reps*B, H, W, cpad), zero padded (into ``out`` if given)."""
     B, ca, H, W = a.shape
     cb = 0 if b is None else b.shape[1]
     if cpad is None:
         cpad = (ca + cb + 3) // 4 * 4
-    out = _empty((reps * B, H, W, cpad), a)
+    if out is None:
+        out = _empty((reps * B, H, W, cpad), a)
+    elif tuple(out.shape) != (reps * B, H, W, cpad):
+        raise ValueError(f'assemble_input: out has shape {tuple(out.shape)}, expected {(reps * B, H, W, cpad)}')
     call('dmh_assemble_input', ptr(a), ca, ptr(b), cb, ptr(m), ptr(out), B, reps, H * W, cpad)
     return out
 
@@ -438,6 +441,31 @@ def sampler_step_dev(cur, model_cond, model_null, x, noise, out=None, keep=None)
     img = torch.empty_like(x) if out is None else out
     call('dmh_sampler_step_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(noise), ptr(img),
          None, None, x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img
+
+
+def sampler_step_ddp_dev(cur, cursor, draws, model_out, img, noise=None, sample_ids=None, state=None, x_start=None, xin=None,
+                         self_cond=False):
+    """the replayed step of the unconditional loop in one launch (dmh_sampler_step_ddp_dev), in place on img (B,C,H,W):
+    entry ``cur`` of step_table, its noise from the keyed generator (sample_ids + state) or ``noise`` when draws[cursor] != 0,
+    x_start (B,C,H,W) if given, and the next step's network input ``xin`` (B,H,W,cpad) — cat(x_start, img) with self_cond,
+    img without — if given."""
+    B, Cc, H, W = img.shape
+    for t in (model_out, noise, x_start):
+        if t is not None and tuple(t.shape) != (B, Cc, H, W):
+            raise ValueError(f'sampler_step_ddp_dev: {tuple(t.shape)} against img {(B, Cc, H, W)}')
+    cin = Cc * (2 if self_cond else 1)
+    if xin is not None:
+        if xin.dim() != 4 or tuple(xin.shape[:3]) != (B, H, W):
+            raise ValueError(f'sampler_step_ddp_dev: xin {tuple(xin.shape)} against img {(B, Cc, H, W)}')
+        cpad = xin.shape[3]
+    else:
+        cpad = (cin + 3) // 4 * 4
+    if sample_ids is not None and sample_ids.shape[0] < B:
+        raise ValueError(f'sampler_step_ddp_dev: {sample_ids.shape[0]} sample ids for {B} rows')
+    call('dmh_sampler_step_ddp_dev', ptr(cur, torch.uint8), ptr(cursor, torch.int32), ptr(draws, torch.int32), ptr(model_out),
+         ptr(img), ptr(noise), ptr(sample_ids, torch.int64), ptr(state, torch.int64), ptr(x_start), ptr(xin), B, Cc, H * W, cpad,
+         int(bool(self_cond)))
     return img
 
 

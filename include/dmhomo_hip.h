@@ -300,6 +300,19 @@ int dmh_sampler_step_dev(const DmhStep* cur_dev, const float* model_cond, const 
 int dmh_sampler_seek(int32_t* cursor, int k, const DmhStep* table, const int64_t* times, int S, DmhStep* cur,
                      int64_t* tcond, int B, void* stream);
 
+/* The replayed step of the UNCONDITIONAL loop (p_sample_loop / ddim_sample, DDP:647-729) in one launch: the step of
+ * dmh_sampler_step_dev (entry *cur_dev, no model_null) applied in place to img [B][C][HW], plus its noise and the next step's
+ * network input.  draws: [S] int32 device table next to the step table, indexed by *cursor: 0 for an entry that the eager loop
+ * runs without noise (t == 0 of the ancestral loop, the last DDIM step) — it neither draws nor advances the generator.
+ * Noise source (at most one): sample_ids + state = the keyed generator of dmh_rng_indexed (kind 0), drawn in the kernel with
+ * the same counter layout, so bit-identical to what dmh_rng_indexed would have stored, and the draw index advanced once per
+ * drawing launch as dmh_rng_indexed advances it; or noise [B][C][HW] (e.g. torch.randn).  A drawing entry without a source
+ * yields NaN.  x_start (optional): [B][C][HW].  xin_next (optional): NHWC [B][HW][cpad] = cat(x_start, img) with self_cond,
+ * img without, zero padded: what dmh_assemble_input builds for the next step (DDP:411).  cpad: multiple of 4 >= C*(1+self_cond). */
+int dmh_sampler_step_ddp_dev(const DmhStep* cur_dev, const int32_t* cursor, const int32_t* draws, const float* model_out,
+                             float* img, const float* noise, const int64_t* sample_ids, uint64_t* state, float* x_start,
+                             float* xin_next, int B, int C, int HW, int cpad, int self_cond, void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =
