@@ -73,6 +73,8 @@ SIGNATURES = {
     'dmh_conv_wgrad_workspace_floats': (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'dmh_conv_wgrad': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int,
                                c_int, c_int, c_int, C.c_void_p]),
+    'dmh_conv_unshuffle_wgrad_workspace_floats': (c_i64, [c_int, c_int, c_int, c_int, c_int]),
+    'dmh_conv_unshuffle_wgrad': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
     'dmh_s2d_shift': (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, C.c_void_p]),
     'dmh_d2s': (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, C.c_void_p]),
     'dmh_sumpool2': (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, C.c_void_p]),
@@ -94,6 +96,7 @@ SIGNATURES = {
     'dmh_softmax_rows_backward': (c_int, [c_f32p, c_f32p, c_i64, c_int, C.c_void_p]),
     'dmh_act': (c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_int, C.c_void_p]),
     'dmh_class_embed_backward': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_loss_backward_ddp': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, c_float, C.c_void_p]),
     'dmh_loss_backward': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int,
                                   C.c_void_p]),
     'dmh_sumsq_blocks': (c_int, []),

@@ -53,8 +53,13 @@ struct WgArgs {
   int ablate;  // diagnostics (DMH_WG_ABL): 1 skip the MFMA phase, 2 skip the global loads, 4 skip the split + LDS writes, 8 skip the partial store
 };
 
-template <int KH, int NCB, int PAD>
+// UNSH (KH = 1 only): the input is the pixel-unshuffled view of the stored x [B][2H][2W][C0/4] (the DDP Downsample,
+// DDP:110-113), read in place: channel j = (py*2+px)*C + c of output pixel (y, x) is x[b][2y+py][2x+px][c], so the 4C
+// channels of a pixel are two contiguous runs of 2C floats (rows 2y and 2y+1); the reduce kernel restores the reference's
+// channel order c*4 + py*2 + px.
+template <int KH, int NCB, int PAD, bool UNSH = false>
 __global__ __launch_bounds__(256, NCB == 4 ? 2 : 1) void conv_wgrad_kernel(WgArgs p) {
+  static_assert(!UNSH || (KH == 1 && PAD == 0), "the unshuffled input is a 1x1 conv's");
   using Cfg = WgCfg<KH, NCB, PAD>;
   constexpr int NT = Cfg::NT, XW = Cfg::XW, XPIX = Cfg::XPIX, DPX = Cfg::DPX, XQ = Cfg::XQ;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -99,7 +104,15 @@ __global__ __launch_bounds__(256, NCB == 4 ? 2 : 1) void conv_wgrad_kernel(WgArg
     for (int i = 0; i < Cfg::NX; ++i) {
       const int slot = tid + 256 * i;
       const int pix = slot / XQ, qx = slot % XQ;
-      if (pix < XPIX) {
+      if (UNSH && pix < XPIX) {
+        const int y = oy0 + pix / XW, x = ox0 + pix % XW, j = c0 + qx * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (y < p.H && x < p.W && j < Cin) {
+          const int run = Cin >> 1, py = j >= run ? 1 : 0;  // run = 2C: the two input rows of the output pixel
+          v = ld4(p.src0 + ((size_t)(b * p.Hin + 2 * y + py) * p.Win + 2 * x) * (Cin >> 2) + (j - py * run));
+        }
+        st4(xt + pix * DPX + qx * 4, v);
+      } else if (pix < XPIX) {
         const int y = oy0 - PAD + pix / XW, x = ox0 - PAD + pix % XW, c = c0 + qx * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (y >= 0 && y < Hv && x >= 0 && x < Wv && c < Cin) {
@@ -534,6 +547,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_v2_kernel(const float* 
 // dW[o][c][tap] (OIHW, Cin = C0 + C1) = sum over the pixel splits; same for db.  A workgroup owns 64 consecutive outputs
 // (one 256-byte row of every partial block: coalesced) and spreads the splits over its 4 waves: wave g adds splits
 // g, g+4, ... in order, then the four sums are combined as (s0 + s1) + (s2 + s3) — a fixed tree, the same bits every run.
+// UNSH: the partial blocks hold channel j = (py*2+px)*C + c of the unshuffled input; dw gets it at c*4 + py*2 + px.
+template <bool UNSH = false>
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ part_w,
                                                                 const float* __restrict__ part_b, float* __restrict__ dw,
                                                                 float* __restrict__ db, int Cout, int Cin, int NT,
@@ -545,7 +560,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
   float s = 0.f;
   if (idx < total) {
     const int t = idx % NT;
-    const int c = (idx / NT) % Cin;
+    const int cr = (idx / NT) % Cin;
+    const int c = UNSH ? (cr & 3) * (Cin >> 2) + (cr >> 2) : cr;  // channel of the partial block
     const int o = idx / ((int64_t)NT * Cin);
     const int pair = (o / 64) * ctiles + c / cw;  // cw input channels per workgroup block (64, or 16 for the 7x7 conv)
     const size_t off = ((size_t)pair * 64 * 64 + (size_t)(o % 64) * 64 + c % cw) * NT + t;
@@ -716,10 +732,63 @@ extern "C" int dmh_conv_wgrad(const float* dy, const float* src0, const float* s
     }
     DMH_CHECK_LAUNCH("dmh_conv_wgrad");
     const int64_t total = (int64_t)Cout * (a.C0 + a.C1) * KH * KH;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)cdiv64(total, 64)), dim3(256), 0, st, a.part_w, a.part_b, dw,
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel<false>, dim3((unsigned)cdiv64(total, 64)), dim3(256), 0, st, a.part_w, a.part_b, dw,
                        db, Cout, a.C0 + a.C1, KH * KH, a.nsplit, otiles, a.ctiles, cw);
   }
   DMH_CHECK_LAUNCH("dmh_conv_wgrad(reduce)");
+  return DMH_OK;
+}
+
+// ------------------------------------------------------------------------------------------ DDP Downsample
+// weight / bias gradient of pixel-unshuffle + 1x1 (DDP:110-113), which the forward runs as a 2x2 / stride-2 'valid' conv:
+//   dW22[o][c][py][px] = sum_{b,y,x} dy[b][y][x][o] * x[b][2y+py][2x+px][c],   db[o] = sum dy[...][o]
+// = the 1x1 wgrad above (exact fp32 MFMA, pixels as K split over workgroups, fixed-order reduce) over the unshuffled view
+// of x, which its staging reads in place.  H, W: size of x (even); dy is [B][H/2][W/2][Cout].
+static bool unshuffle_dims_ok(int B, int H, int W, int C, int Cout) {
+  return dmh_dims_ok({B, H, W, C, Cout}) && dmh_dims_ok({4ll * C}) && H % 2 == 0 && W % 2 == 0 &&
+         (long long)B * H * W <= (1ll << 31) - 1;
+}
+extern "C" int64_t dmh_conv_unshuffle_wgrad_workspace_floats(int B, int H, int W, int C, int Cout) {
+  if (!unshuffle_dims_ok(B, H, W, C, Cout)) return -1;
+  const int npairs = cdiv(Cout, 64) * cdiv(4 * C, 64);
+  const int ns = wgrad_splits(B * cdiv(H / 2, TH) * cdiv(W / 2, TW), npairs);
+  return (int64_t)ns * npairs * 64 * 64 + (int64_t)ns * cdiv(Cout, 64) * 64;
+}
+
+extern "C" int dmh_conv_unshuffle_wgrad(const float* dy, const float* x, float* dw, float* db, float* work, int B, int H,
+                                        int W, int C, int Cout, void* stream) {
+  DMH_REQUIRE(dy && x && dw && work, "dmh_conv_unshuffle_wgrad: null pointer");
+  DMH_REQUIRE(unshuffle_dims_ok(B, H, W, C, Cout) && C % 4 == 0 && Cout % 4 == 0,
+              "dmh_conv_unshuffle_wgrad: bad shape (B=%d H=%d W=%d C=%d Cout=%d: H, W even, C, Cout multiples of 4)", B, H, W,
+              C, Cout);
+  hipStream_t st = (hipStream_t)stream;
+  WgArgs a = {};
+  a.dy = dy;
+  a.src0 = x;
+  a.B = B;
+  a.H = H / 2;
+  a.W = W / 2;
+  a.C0 = 4 * C;
+  a.Cout = Cout;
+  a.Hin = H;
+  a.Win = W;
+  a.tilesX = cdiv(a.W, TW);
+  a.tilesY = cdiv(a.H, TH);
+  a.nitems = B * a.tilesX * a.tilesY;
+  a.ctiles = cdiv(a.C0, 64);
+  const int otiles = cdiv(Cout, 64), npairs = otiles * a.ctiles;
+  a.nsplit = wgrad_splits(a.nitems, npairs);
+  a.part_w = work;
+  a.part_b = work + (int64_t)a.nsplit * npairs * 64 * 64;
+  auto kern = conv_wgrad_kernel<1, 4, 0, true>;
+  constexpr int lds = WgCfg<1, 4, 0>::LDS_BYTES;  // 40 KB: no opt-in needed
+  hipLaunchKernelGGL(kern, dim3(a.nsplit, npairs), dim3(256), lds, st, a);
+  DMH_CHECK_LAUNCH("dmh_conv_unshuffle_wgrad");
+  const int64_t total = (int64_t)Cout * a.C0;
+  auto red = conv_wgrad_reduce_kernel<true>;
+  hipLaunchKernelGGL(red, dim3((unsigned)cdiv64(total, 64)), dim3(256), 0, st, a.part_w, a.part_b,
+                     dw, db, Cout, a.C0, 1, a.nsplit, otiles, a.ctiles, 64);
+  DMH_CHECK_LAUNCH("dmh_conv_unshuffle_wgrad(reduce)");
   return DMH_OK;
 }
 

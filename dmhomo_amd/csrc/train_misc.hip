@@ -184,6 +184,33 @@ extern "C" int dmh_loss_backward(const float* out, const float* target, const fl
   DMH_CHECK_LAUNCH("dmh_loss_backward(warp)");
   return DMH_OK;
 }
+// ---- gradient of the unconditional p_losses (DDP:804-811) wrt the UNet output, NCHW [B][per]:
+// loss = mean_b w[b] * mean_per l(out - target)  ->  dout = scale * w[b] * g(out - target) / (B * per), g = sign (L1, torch's
+// sign(0) = 0) or 2 d (L2); scale folds in 1 / accum.  Elementwise, grid-stride, bound by HBM.
+__global__ __launch_bounds__(256) void ddp_loss_bwd_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                           const float* __restrict__ w, float* __restrict__ dout, int B,
+                                                           int64_t per, int squared, float scale) {
+  const int64_t total = (int64_t)B * per;
+  const float inv = 1.0f / ((float)B * (float)per);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const float n = scale * w[i / per] * inv;
+    const float d = out[i] - target[i];
+    dout[i] = squared ? 2.0f * d * n : (d > 0.f ? n : (d < 0.f ? -n : 0.f));
+  }
+}
+
+extern "C" int dmh_loss_backward_ddp(const float* out, const float* target, const float* w, float* dout, int B, int64_t per,
+                                     int squared, float scale, void* stream) {
+  DMH_REQUIRE(out && target && w && dout, "dmh_loss_backward_ddp: null pointer");
+  DMH_REQUIRE(B > 0 && per > 0 && per <= ((int64_t)1 << 40) / B && (squared == 0 || squared == 1),
+              "dmh_loss_backward_ddp: bad arguments (B=%d per=%lld squared=%d)", B, (long long)per, squared);
+  const int64_t blocks = cdiv64((int64_t)B * per, 256);
+  hipLaunchKernelGGL(ddp_loss_bwd_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, out,
+                     target, w, dout, B, per, squared, scale);
+  DMH_CHECK_LAUNCH("dmh_loss_backward_ddp");
+  return DMH_OK;
+}
+
 #define DMH_SUMSQ_BLOCKS 256
 extern "C" int dmh_sumsq_blocks(void) { return DMH_SUMSQ_BLOCKS; }
 // part: f64 [dmh_sumsq_blocks()] for this tensor

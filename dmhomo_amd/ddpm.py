@@ -337,11 +337,38 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
     _random = staticmethod(__import__('random').random)      # the `random() < 0.5` self-conditioning draw of DDP:785
 
-    @torch.no_grad()
     def p_losses(self, x_start, t, noise=None):
-        """DDP:772-811, FORWARD VALUE: q_sample -> (self-conditioning pass, half of the time) -> UNet -> per-sample L1 / L2
-        mean -> x p2_loss_weight[t] -> mean.  The DGM trains the conditional class (classifier_free_guidance, built with
-        its backward in dmhomo_amd.train); this unconditional twin returns the loss value without an autograd graph."""
+        """DDP:772-811: q_sample -> (self-conditioning pass, half of the time) -> UNet -> per-sample L1 / L2 mean ->
+        x p2_loss_weight[t] -> mean.  With grad mode on and a model parameter that requires grad, the loss carries a
+        grad_fn: dmhomo_amd.train.DDPTrainStep computes it and every parameter gradient on the HIP backward kernels, and
+        ``loss.backward()`` hands those to autograd.  Otherwise (torch.no_grad()) only the value is computed."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.model.parameters()):
+            from .train import ddp_loss_with_grad_fn
+            return ddp_loss_with_grad_fn(self, x_start, t, noise)
+        with torch.no_grad():
+            return self._p_losses_value(x_start, t, noise)
+
+    def _pred_x_start(self, x, t, model_out):
+        """model_predictions(x, t, ...).pred_x_start for a given UNet output (DDP:582-600, no clamp): per-sample
+        coefficients, t differs from row to row"""
+        if self.objective == 'pred_x0':
+            return model_out
+        ca = (self.sqrt_recip_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_alphas_cumprod)
+        cb = (self.sqrt_recipm1_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_one_minus_alphas_cumprod)
+        return ops.q_sample(x, model_out.contiguous(), ca.gather(-1, t).contiguous(), (-cb).gather(-1, t).contiguous())
+
+    def _loss_target(self, x_start, t, noise):
+        if self.objective == 'pred_noise':
+            return noise
+        if self.objective == 'pred_x0':
+            return x_start
+        if self.objective == 'pred_v':                       # predict_v, DDP:596-598
+            return ops.q_sample(noise, x_start, self.sqrt_alphas_cumprod.gather(-1, t).contiguous(),
+                                (-self.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous())
+        raise ValueError(f'unknown objective {self.objective}')
+
+    def _p_losses_value(self, x_start, t, noise=None):
+        """DDP:772-811, forward value only"""
         squared = self.loss_fn == 'l2'
         x_start = x_start.to(torch.float32).contiguous()
         noise = default(noise, lambda: self.rng.randn(x_start.shape, x_start.device)).to(torch.float32).contiguous()
@@ -350,24 +377,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         x_self_cond = None
         if self.self_condition and self._random() < 0.5:
             out0 = self.model(x, t, None)                    # model_predictions(x, t).pred_x_start, DDP:787 (no clamp)
-            if self.objective == 'pred_x0':
-                x_self_cond = out0
-            else:                                            # per-sample coefficients: t differs from row to row
-                ca = (self.sqrt_recip_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_alphas_cumprod)
-                cb = (self.sqrt_recipm1_alphas_cumprod if self.objective == 'pred_noise'
-                      else self.sqrt_one_minus_alphas_cumprod)
-                x_self_cond = ops.q_sample(x, out0.contiguous(), ca.gather(-1, t).contiguous(),
-                                           (-cb).gather(-1, t).contiguous())
+            x_self_cond = self._pred_x_start(x, t, out0)
         model_out = self.model(x, t, x_self_cond)
-        if self.objective == 'pred_noise':
-            target = noise
-        elif self.objective == 'pred_x0':
-            target = x_start
-        elif self.objective == 'pred_v':                     # predict_v, DDP:596-598
-            target = ops.q_sample(noise, x_start, self.sqrt_alphas_cumprod.gather(-1, t).contiguous(),
-                                  (-self.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous())
-        else:
-            raise ValueError(f'unknown objective {self.objective}')
+        target = self._loss_target(x_start, t, noise)
         loss = ops.diff_mean(model_out, target, None, squared)                         # (B,) per-sample means
         w = self.p2_loss_weight.gather(-1, t).contiguous()
         return ops.loss_combine(torch.zeros_like(loss), loss, w)                       # mean(loss * w), DDP:810-811

@@ -864,6 +864,47 @@ def conv_down_backward(dy, x, w, dpack=None):
     return dx, dw, db
 
 
+def conv_unshuffle_wgrad(dy, x, want_bias=True):
+    """weight (and bias) gradient of the DDP Downsample = pixel-unshuffle + 1x1 (DDP:110-113): dy (B,H/2,W/2,Cout),
+    x (B,H,W,C) the stored input, read in place -> dw (Cout, 4C, 1, 1) in the reference's channel order c*4 + py*2 + px"""
+    B, H, W, c = x.shape
+    cout = dy.shape[3]
+    assert tuple(dy.shape) == (B, H // 2, W // 2, cout), (dy.shape, x.shape)
+    dw = _empty((cout, 4 * c, 1, 1), dy)
+    db = _empty((cout,), dy) if want_bias else None
+    work = _empty((lib().dmh_conv_unshuffle_wgrad_workspace_floats(B, H, W, c, cout),), dy)
+    call('dmh_conv_unshuffle_wgrad', ptr(dy.contiguous()), ptr(x.contiguous()), ptr(dw), ptr(db), ptr(work), B, H, W, c, cout)
+    return (dw, db) if want_bias else dw
+
+
+def conv_unshuffle_dgrad_pack(w, batch=None):
+    """PackedConv of the 1x1 conv over dy that yields the data gradient of the DDP Downsample (weight w (Cout, 4C, 1, 1))
+    in pixel-shuffle layout: out[m][l][(py*2+px)*C + c] = dx[2m+py][2l+px][c] (then dmh_d2s).  The transposed, permuted
+    weight is re-derived from w on every ``batch.run()``."""
+    cout, c4 = w.shape[0], w.shape[1]
+    c = c4 // 4
+    wt = torch.empty((c4, cout, 1, 1), device=w.device, dtype=torch.float32)
+    w_src = w.detach()
+
+    def fill():                            # wt[(py*2+px)*C + c][o] = w[o][c*4 + py*2 + px]
+        wt.view(4, c, cout).copy_(w_src.view(cout, c, 4).permute(2, 1, 0))
+    fill()
+    if batch is not None:
+        batch.pre.append(fill)
+    return PackedConv(wt, None, cout, batch=batch)
+
+
+def conv_unshuffle_backward(dy, x, w, dpack=None):
+    """backward of the DDP Downsample (DDP:110-113): dy (B,H/2,W/2,Cout), x (B,H,W,C), w (Cout, 4C, 1, 1) -> dx, dw, db"""
+    B, H, W, c = x.shape
+    dpack = dpack or conv_unshuffle_dgrad_pack(w)
+    g4 = conv2d(dpack, dy)                                              # (B, H/2, W/2, 4C)
+    dx = torch.empty_like(x)
+    call('dmh_d2s', ptr(g4), ptr(dx), B, H // 2, W // 2, c)
+    dw, db = conv_unshuffle_wgrad(dy, x)
+    return dx, dw, db
+
+
 def act(x, mode, dy=None):
     """mode 'silu' | 'gelu': f(x), or dy * f'(x) when dy is given."""
     x = x.contiguous()
@@ -909,6 +950,17 @@ def loss_backward(out, target, warped, mask, flow, abar, squared=False):
     gD = torch.empty((B, 3, H, W), device=out.device, dtype=F32)
     call('dmh_loss_backward', ptr(out), ptr(target.contiguous()), ptr(warped), ptr(mask.contiguous()),
          ptr(flow.contiguous()), ptr(abar.contiguous()), ptr(dout), ptr(gD), B, H, W, int(bool(squared)))
+    return dout
+
+
+def loss_backward_ddp(out, target, w, squared=False, scale=1.0):
+    """gradient of the unconditional p_losses (DDP:804-811) wrt the UNet output (B,C,H,W): w (B,) = p2_loss_weight[t];
+    ``scale`` folds in 1 / accum"""
+    out = out.contiguous()
+    B = out.shape[0]
+    dout = torch.empty_like(out)
+    call('dmh_loss_backward_ddp', ptr(out), ptr(target.contiguous()), ptr(w.to(F32).contiguous()), ptr(dout), B,
+         out.numel() // B, int(bool(squared)), float(scale))
     return dout
 
 

@@ -13,7 +13,9 @@ csrc/norm_backward.hip:
 ``UnetTrain`` strings those blocks, the attention / LayerNorm / embedding / resampling-conv backward kernels into the
 whole conditional UNet (CFG:412-466) with a manual tape; ``TrainStep`` adds p_losses (CFG:770-806) with its gradient,
 gradient accumulation, the global-norm clip, Adam and the RCCL gradient all-reduce: one optimiser step of
-``Trainer.train`` (DDP:1830-1862).  There is no autograd anywhere on this path.
+``Trainer.train`` (DDP:1830-1862).  ``DDPTrainStep`` does the same for the unconditional ddpm.GaussianDiffusion (DDP:772-820)
+on the same UnetTrain.  There is no autograd anywhere on this path; ``_PLoss`` / ``_PLossDDP`` hand the finished gradients
+to autograd when a user calls ``loss.backward()``.
 """
 import os
 
@@ -144,14 +146,20 @@ class _LinAttn:
 
 
 class _Conv:
-    """plain biased conv of the trunk: kind 'same3' (3x3), 'down4' (4x4 / stride 2), 'up3' (nearest x2 + 3x3), 'init7'."""
+    """plain biased conv of the trunk: kind 'same3' (3x3), 'down4' (4x4 / stride 2), 'up3' (nearest x2 + 3x3), 'init7',
+    'unshuffle' (the DDP Downsample, pixel-unshuffle + 1x1 (DDP:110-113): w (Cout, 4C, 1, 1), run as 2x2 / stride 2)."""
 
     def __init__(self, w, b, kind, c, batch=None):
         self.w, self.b, self.kind, self.c = w, b, kind, c
         k = w.shape[-1]
-        self.f = ops.PackedConv(w, b, c, 0, 2 if kind == 'down4' else 1, 1 if kind == 'up3' else 0, batch=batch)
+        if kind == 'unshuffle':           # (a view of the parameter: the forward image follows it on every repack)
+            self.f = ops.PackedConv(w.reshape(w.shape[0], c, 2, 2), b, c, 0, 2, batch=batch)
+        else:
+            self.f = ops.PackedConv(w, b, c, 0, 2 if kind == 'down4' else 1, 1 if kind == 'up3' else 0, batch=batch)
         self.d = None
-        if kind in ('same3', 'up3'):
+        if kind == 'unshuffle':
+            self.d = ops.conv_unshuffle_dgrad_pack(w, batch=batch)
+        elif kind in ('same3', 'up3'):
             self.d = ops.conv_dgrad_pack(w, c, batch=batch)
         elif kind == 'down4':
             self.d = ops.conv_down_dgrad_pack(w, batch=batch)
@@ -165,6 +173,8 @@ class _Conv:
             return ops.conv_down_backward(dy, x, self.w, self.d)
         if self.kind == 'up3':
             return ops.conv_up_backward(dy, x, self.w, self.d)
+        if self.kind == 'unshuffle':
+            return ops.conv_unshuffle_backward(dy, x, self.w, self.d)
         dw, db = ops.conv_wgrad(dy, x, k=self.k)
         dx = ops.conv2d(self.d, dy) if (want_dx and self.d is not None) else None
         return dx, dw, db
@@ -172,8 +182,10 @@ class _Conv:
 
 class UnetTrain:
     """forward (saving activations) and backward of classifier_free_guidance.Unet on the HIP kernels.
-    ``module``: a dmhomo_amd.cfg.Unet (same parameter names as the reference).  Gradients come back as
-    {parameter name: tensor of the parameter's shape}."""
+    ``module``: a dmhomo_amd.cfg.Unet (same parameter names as the reference), or a dmhomo_amd.ddpm.Unet (DDP:315-447:
+    no class embedding — the embedding is time only — an optional self-conditioning input, the pixel-unshuffle
+    Downsample): ``forward_uncond`` then stands for ``forward``.  Gradients come back as {parameter name: tensor of the
+    parameter's shape}."""
 
     def __init__(self, module, groups=8):
         self.module, self.groups = module, groups
@@ -199,6 +211,7 @@ class UnetTrain:
             raise NotImplementedError('training a Unet with learned_sinusoidal_cond / random_fourier_features is not supported: '
                                       'the training step has no gradient for RandomOrLearnedSinusoidalPosEmb.weights')
         self.pack = pb = ops.PackBatch()
+        self.uncond = 'classes_emb.weight' not in sd             # ddpm.Unet: time-only embedding
         self.dim = sd['time_mlp.1.weight'].shape[1]
         half = self.dim // 2
         import math
@@ -254,8 +267,12 @@ class UnetTrain:
             res(pfx + '.1', c)
             attn(pfx + '.2', c, True)
             skip_c.append(c)
-            w = sd[pfx + '.3.weight']
-            self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.bias'], 'down4' if w.shape[-1] == 4 else 'same3', c, batch=pb)
+            if (pfx + '.3.1.weight') in sd:                       # DDP: pixel-unshuffle + 1x1
+                w = sd[pfx + '.3.1.weight']
+                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.1.bias'], 'unshuffle', c, batch=pb)
+            else:
+                w = sd[pfx + '.3.weight']
+                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.bias'], 'down4' if w.shape[-1] == 4 else 'same3', c, batch=pb)
             c = w.shape[0]
         res('mid_block1', c)
         attn('mid_attn', c, False)
@@ -293,6 +310,9 @@ class UnetTrain:
         h1 = self._lin(se, sd['time_mlp.1.weight'], sd['time_mlp.1.bias'])
         a1 = ops.act(h1, 'gelu')
         temb = self._lin(a1, sd['time_mlp.3.weight'], sd['time_mlp.3.bias'])
+        if self.uncond:                                          # DDP:417: the conditioning is the time embedding alone
+            ac = ops.act(temb, 'silu')
+            return self._lin(ac, self.mlp_w, self.mlp_b), dict(se=se, h1=h1, a1=a1, cond=temb, ac=ac)
         ce = ops.class_embed(classes, keep, sd['classes_emb.weight'], sd['null_classes_emb'])
         h2 = self._lin(ce, sd['classes_mlp.0.weight'], sd['classes_mlp.0.bias'])
         a2 = ops.act(h2, 'gelu')
@@ -311,6 +331,11 @@ class UnetTrain:
             g[k + '.mlp.1.weight'], g[k + '.mlp.1.bias'] = dw[off:off + n2].contiguous(), db[off:off + n2].contiguous()
             off += n2
         dcond = ops.act(sv['cond'], 'silu', dy=dac)
+        if self.uncond:
+            da1, g['time_mlp.3.weight'], g['time_mlp.3.bias'] = ops.linear_backward(sv['a1'], sd['time_mlp.3.weight'], dcond)
+            dh1 = ops.act(sv['h1'], 'gelu', dy=da1)
+            _, g['time_mlp.1.weight'], g['time_mlp.1.bias'] = ops.linear_backward(sv['se'], sd['time_mlp.1.weight'], dh1)
+            return
         td = sd['time_mlp.3.weight'].shape[0]
         dtemb, dcemb = dcond[:, :td].contiguous(), dcond[:, td:].contiguous()
         da1, g['time_mlp.3.weight'], g['time_mlp.3.bias'] = ops.linear_backward(sv['a1'], sd['time_mlp.3.weight'], dtemb)
@@ -329,10 +354,26 @@ class UnetTrain:
     def forward(self, x, time, classes, rgb_flow, mask, keep, taps=None):
         """x (B,6,H,W), rgb_flow (B,3,H,W), mask (B,1,H,W) NCHW fp32, time/classes (B,) int64, keep (B,) bool
         -> out (B,6,H,W) NCHW, saved"""
-        B = x.shape[0]
         keep = keep.to(torch.uint8).contiguous()
         ss_all, emb = self._embed_forward(time, classes, keep)
         xin = ops.assemble_input(x.contiguous(), rgb_flow.contiguous(), mask.contiguous(), cpad=self.cin_pad)
+        return self._trunk_forward(xin, ss_all, emb, taps)
+
+    def forward_uncond(self, x, time, x_self_cond=None, taps=None):
+        """ddpm.Unet.forward (DDP:408-447): x (B,C,H,W) NCHW fp32, time (B,) int64, x_self_cond (B,C,H,W) or None (zeros
+        when the model self-conditions, DDP:410-411) -> out (B,C,H,W) NCHW, saved"""
+        assert self.uncond, 'forward_uncond is the ddpm.Unet forward; this UnetTrain holds a conditional Unet'
+        x = x.to(torch.float32).contiguous()
+        ss_all, emb = self._embed_forward(time.to(torch.int64).contiguous(), None, None)
+        if self.module.self_condition:                           # the input is cat(x_self_cond, x), DDP:411
+            sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.to(torch.float32).contiguous()
+            xin = ops.assemble_input(sc, x, None, cpad=self.cin_pad)
+        else:
+            xin = ops.assemble_input(x, None, None, cpad=self.cin_pad)
+        return self._trunk_forward(xin, ss_all, emb, taps)
+
+    def _trunk_forward(self, xin, ss_all, emb, taps=None):
+        B = xin.shape[0]
         T = []                                                   # tape: (kind, block name, saved)
 
         def ss(prefix):
@@ -386,7 +427,7 @@ class UnetTrain:
         return out, dict(tape=T, emb=emb, xin=xin, hfinal=h, B=B)
 
     def backward(self, sv, dout):
-        """dout (B,6,H,W) NCHW -> {parameter name: gradient}"""
+        """dout (B,out_dim,H,W) NCHW -> {parameter name: gradient}"""
         g = {}
         sd, T = self.sd, sv['tape']
         B = sv['B']
@@ -459,7 +500,7 @@ class UnetTrain:
             prefix, x0 = pop('conv')
             cv = self.blocks[prefix]
             dx, dw_, db_ = cv.backward(x0, d)
-            wname = prefix + ('.1.weight' if cv.kind == 'up3' else '.weight')
+            wname = prefix + ('.1.weight' if cv.kind in ('up3', 'unshuffle') else '.weight')
             g[wname], g[wname.replace('weight', 'bias')] = dw_, db_
             return dx
 
@@ -667,15 +708,66 @@ class TrainStep:
         """``batches``: ``accum`` pairs (12-channel batch, classes).  -> summed (loss / accum) like DDP:1849."""
         assert len(batches) == self.accum
         total, acc = None, None
-        for i, (img, classes) in enumerate(batches):
+        for i, batch in enumerate(batches):
             kw = draws[i] if draws is not None else {}
-            loss, gr = self.loss_and_grads(img, classes, grad_scale=1.0 / self.accum, **kw)
+            loss, gr = self._batch_loss_and_grads(batch, 1.0 / self.accum, kw)
             acc = gr if acc is None else {k: ops.add(acc[k], gr[k]) for k in acc}
             part = loss / self.accum
             total = part if total is None else total + part
         acc = self._allreduce_mean(acc)
         self.apply(acc)
         return total
+
+    def _batch_loss_and_grads(self, batch, grad_scale, kw):
+        img, classes = batch
+        return self.loss_and_grads(img, classes, grad_scale=grad_scale, **kw)
+
+
+class DDPTrainStep(TrainStep):
+    """TrainStep for the unconditional dmhomo_amd.ddpm.GaussianDiffusion (DDP:481-820): the loss of DDP:772-811 — no
+    photometric term, p2 loss weight, optional self-conditioning — and its gradient, on the same UnetTrain, clip + Adam,
+    re-pack graph and all-reduce as the conditional class.  ``step`` takes ``accum`` image batches (B,C,H,W) in [0,1]."""
+
+    def loss_and_grads(self, img, t=None, noise=None, use_self_cond=None, grad_scale=1.0):
+        """DDP:813-820 on ``img`` in [0,1] -> (loss (0-dim tensor, unscaled), {parameter name: d(grad_scale * loss)/d
+        parameter}).  ``t``, ``noise``, ``use_self_cond`` default to the reference's draws, in its order (DDP:817 randint,
+        DDP:774 randn_like, DDP:785 random() < 0.5)."""
+        df = self.diffusion
+        b, c, h, w = img.shape
+        assert h == df.image_size and w == df.image_size, f'height and width of image must be {df.image_size}'
+        if t is None:
+            t = torch.randint(0, df.num_timesteps, (b,), device=img.device).long()
+        return self.p_losses_and_grads(ops.affine(img.to(torch.float32), 2., -1.), t, noise, use_self_cond, grad_scale)
+
+    def p_losses_and_grads(self, x_start, t, noise=None, use_self_cond=None, grad_scale=1.0):
+        """DDP:772-811 on a normalised x_start and given t"""
+        df, ut = self.diffusion, self.ut
+        self.ensure_fresh()
+        x_start = x_start.to(torch.float32).contiguous()
+        if noise is None:
+            noise = df.rng.randn(x_start.shape, x_start.device)
+        noise = noise.to(torch.float32).contiguous()
+        t = t.to(torch.int64).contiguous()
+        squared = df.loss_fn == 'l2'
+        x = df.q_sample(x_start, t, noise)
+        if use_self_cond is None:
+            use_self_cond = bool(df.self_condition) and df._random() < 0.5
+        x_self_cond = None
+        if use_self_cond and df.self_condition:
+            # model_predictions(x, t).pred_x_start (DDP:787, no clamp) with the current weights, a constant of the loss;
+            # its saved activations are dropped unused
+            out0, _ = ut.forward_uncond(x, t, None)
+            x_self_cond = df._pred_x_start(x, t, out0)
+        out, saved = ut.forward_uncond(x, t, x_self_cond)
+        target = df._loss_target(x_start, t, noise)
+        w = df.p2_loss_weight.gather(-1, t).to(torch.float32).contiguous()
+        per = ops.diff_mean(out, target, None, squared)                                 # (B,) per-sample means
+        loss = ops.loss_combine(torch.zeros_like(per), per, w)                          # mean(loss * w), DDP:810-811
+        dout = ops.loss_backward_ddp(out, target, w, squared, grad_scale)
+        return loss, ut.backward(saved, dout)
+
+    def _batch_loss_and_grads(self, batch, grad_scale, kw):
+        return self.loss_and_grads(batch, grad_scale=grad_scale, **kw)
 
 
 class _PLoss(torch.autograd.Function):
@@ -702,3 +794,29 @@ def loss_with_grad_fn(diffusion, img, classes):
         ts = TrainStep(diffusion)
         diffusion.__dict__['_dmh_train_step'] = ts        # not a submodule / parameter: plain attribute
     return _PLoss.apply(ts, img, classes, *ts.params.values())
+
+
+class _PLossDDP(torch.autograd.Function):
+    """autograd boundary of ddpm.GaussianDiffusion.p_losses: DDPTrainStep produces the loss and every parameter gradient
+    together; backward() hands the gradients to autograd, scaled by the incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, ts, x_start, t, noise, *params):
+        loss, grads = ts.p_losses_and_grads(x_start, t, noise)
+        ctx.grads = [grads.get(k) for k in ts.params]
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        s = float(gout)
+        out = [None if g is None else (g if s == 1.0 else ops.affine(g, s, 0.)) for g in ctx.grads]
+        ctx.grads = None
+        return (None, None, None, None, *out)
+
+
+def ddp_loss_with_grad_fn(diffusion, x_start, t, noise=None):
+    ts = diffusion.__dict__.get('_dmh_train_step')
+    if not isinstance(ts, DDPTrainStep):
+        ts = DDPTrainStep(diffusion)
+        diffusion.__dict__['_dmh_train_step'] = ts        # not a submodule / parameter: plain attribute
+    return _PLossDDP.apply(ts, x_start, t, noise, *ts.params.values())

@@ -402,6 +402,16 @@ int dmh_dlt_homography(const float* flow, double* ws, double* Hout, int B, int H
 int64_t dmh_conv_wgrad_workspace_floats(int B, int H, int W, int C0, int C1, int Cout, int KH);
 int dmh_conv_wgrad(const float* dy, const float* src0, const float* src1, const float* in_coef, float* dw, float* db,
                    float* work, int B, int H, int W, int C0, int C1, int Cout, int KH, int ups, void* stream);
+/* weight / bias gradient of the DDP Downsample, pixel-unshuffle + 1x1 (DDP:110-113), with W22 = weight.reshape(Cout, C, 2, 2):
+ *   dw[o][c*4 + py*2 + px] = sum_{b,y,x} dy[b][y][x][o] * x[b][2y+py][2x+px][c],  db[o] = sum dy[b][y][x][o]
+ * x: the stored NHWC input [B][H][W][C] (H, W even), read in place (no space-to-depth copy); dy [B][H/2][W/2][Cout];
+ * dw [Cout][4C] (the reference's (Cout, 4C, 1, 1)); db [Cout] or NULL; work: ..._workspace_floats floats (-1: bad sizes).
+ * The contract of dmh_conv_wgrad's KH = 1: exact fp32 (v_mfma_f32_16x16x4_f32), pixels as K split over workgroups, the
+ * splits reduced in a fixed order (deterministic).  C, Cout multiples of 4.  The DATA gradient is the 1x1 dmh_conv2d of dy
+ * with W22 transposed to [(py*2+px)*C + c][Cout] followed by dmh_d2s. */
+int64_t dmh_conv_unshuffle_wgrad_workspace_floats(int B, int H, int W, int C, int Cout);
+int dmh_conv_unshuffle_wgrad(const float* dy, const float* x, float* dw, float* db, float* work, int B, int H, int W, int C,
+                             int Cout, void* stream);
 /* layout helpers of the strided / upsampled convs' backward:
  *   dmh_s2d_shift  X[b][cy][cx][(py*2+px)*C + c] = x[b][2cy-1+py][2cx-1+px][c] (0 outside), [B][H/2+1][W/2+1][4C]
  *   dmh_d2s        out[b][2m+ry][2l+rx][c] = in[b][m][l][(ry*2+rx)*C + c]        [B][H][W][4C] -> [B][2H][2W][C]
@@ -461,6 +471,11 @@ int dmh_class_embed_backward(const float* d, const int64_t* classes, const unsig
  * work.  The transpose of the bilinear gather uses float atomics (order not fixed where the flow field folds). */
 int dmh_loss_backward(const float* out, const float* target, const float* warped, const float* mask, const float* flow,
                       const float* abar, float* dout, float* gD, int B, int H, int W, int squared, void* stream);
+/* gradient of the unconditional p_losses (DDP:804-811) wrt the UNet output: out, target NCHW [B][per] (per = C*H*W);
+ * w [B] = p2_loss_weight[t];  dout = scale * w[b] * g(out - target) / (B * per), g = sign (L1, sign(0) = 0; squared = 0) or
+ * 2 d (L2; squared = 1); scale: 1 / accum of gradient accumulation. */
+int dmh_loss_backward_ddp(const float* out, const float* target, const float* w, float* dout, int B, int64_t per, int squared,
+                          float scale, void* stream);
 /* optimiser (DDP:1852-1862): per-tensor partial sums of squares (f64 [dmh_sumsq_blocks()] each) -> global norm and clip
  * coefficient (norm_out[0], norm_out[1] = min(1, max_norm / (norm + 1e-6))) -> Adam with the gradient scaled by
  * gscale[1] (torch.optim.Adam, no weight decay) -> EMA lerp */

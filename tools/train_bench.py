@@ -2,6 +2,7 @@
 """Time the training step (BASELINE config 3: dim 64, 128x128, 16 images per GPU) on the HIP kernels.
 
     python tools/train_bench.py [--bs 16] [--steps 5] [--warmup 2] [--accum 1] [--torch]
+    python tools/train_bench.py --unconditional [--self-cond] ...   # ddpm.GaussianDiffusion (DDP:481-820), one GPU
     torchrun --nproc-per-node N tools/train_bench.py ...        # N ranks, gradients averaged over RCCL
 
 Prints one JSON line: images/s through a full optimiser step (forward, backward, clip, Adam, weight re-pack), and the
@@ -28,7 +29,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--accum', type=int, default=1)
     ap.add_argument('--torch', action='store_true')
-    line = run(ap.parse_args())
+    ap.add_argument('--unconditional', action='store_true', help='train the unconditional class (ddpm.GaussianDiffusion)')
+    ap.add_argument('--self-cond', action='store_true', help='with --unconditional: a self-conditioning model, timed with '
+                    'the self-conditioning draw forced each way')
+    a = ap.parse_args()
+    line = run_uncond(a) if a.unconditional else run(a)
     if line is not None:
         print(json.dumps(line))
 
@@ -109,6 +114,40 @@ def run(a):
     if a.torch and rank == 0:
         line['torch_autograd_same_gpu'] = torch_leg(a, dev)
     return line if rank == 0 else None
+
+
+def run_uncond(a):
+    """ddpm.GaussianDiffusion (pred_noise, L1: the class's defaults) on DDPTrainStep, one GPU: ms per optimiser step and
+    images/s; with --self-cond once with the self-conditioning pass forced on (DDP:785 fires: two UNet forwards) and once
+    forced off"""
+    from dmhomo_amd import ddpm, train
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(1234)
+    m = ddpm.Unet(dim=a.dim, dim_mults=(1, 2, 4, 8), channels=3, self_condition=a.self_cond).to(dev)
+    d = ddpm.GaussianDiffusion(m, image_size=a.size, timesteps=1000, sampling_timesteps=32).to(dev)
+    ts = train.DDPTrainStep(d, lr=5e-4, betas=(0.9, 0.99), accum=a.accum)
+    batches = [torch.rand((a.bs, 3, a.size, a.size), device=dev) for _ in range(a.accum)]
+    modes = {'self_cond_fires': True, 'self_cond_skipped': False} if a.self_cond else {'no_self_cond': None}
+    res = {}
+    for name, use in modes.items():
+        draws = [{} if use is None else {'use_self_cond': use}] * a.accum
+        for _ in range(a.warmup):
+            loss = ts.step(batches, draws=draws)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            loss = ts.step(batches, draws=draws)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.steps
+        res[name] = {'ms_per_step': dt * 1e3, 'images_per_s': a.bs * a.accum / dt, 'loss': float(loss)}
+    first = next(iter(res.values()))
+    return {'metric': f'unconditional training images/sec ({a.size}x{a.size}, optimiser step incl. clip + Adam + weight '
+                      f're-pack)', 'value': first['images_per_s'], 'unit': 'images/s', 'n_gpus': 1,
+            'ms_per_step': first['ms_per_step'], 'modes': res,
+            'config': {'workload': f'DDP Unet dim={a.dim}, self_condition={a.self_cond}, {a.size}x{a.size}, {a.bs} images x '
+                                   f'accum {a.accum}', 'objective': 'pred_noise', 'loss_type': 'l1'},
+            'steps': a.steps, 'warmup': a.warmup, 'higher_is_better': True, 'dtype': 'f32', 'data': 'synthetic'}
 
 
 def torch_leg(a, dev):
