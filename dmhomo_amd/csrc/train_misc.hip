@@ -6,17 +6,30 @@
 //   optimiser  global gradient norm (clip_grad_norm_, DDP:1852), Adam (torch.optim.Adam semantics), EMA lerp
 #include "common.h"
 
-// mode 1 SiLU, 2 GELU (exact, erf)
+// mode 1 SiLU, 2 GELU (exact: Phi(x) = erfc(-x/sqrt2)/2, which keeps its relative accuracy in the negative tail where
+// 1 + erf(x/sqrt2) cancels).  SiLU below -80: expf(-x) overflows from -88.7 on while the result is still a normal float;
+// there sigmoid(x) = e^x to within e^-80, applied as two normal factors e^(x/2) so that only the last product can round
+// into the subnormal range.
 __device__ __forceinline__ float act_fwd(float x, int mode) {
-  if (mode == 1) return x / (1.0f + expf(-x));
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+  if (mode == 1) {
+    if (x < -80.f) {
+      const float e = expf(0.5f * x);
+      return (x * e) * e;
+    }
+    return x / (1.0f + expf(-x));
+  }
+  return 0.5f * x * erfcf(x * -0.70710678118654752440f);
 }
 __device__ __forceinline__ float act_grad(float x, int mode) {
   if (mode == 1) {
-    const float sg = 1.0f / (1.0f + expf(-x));
-    return sg * (1.0f + x * (1.0f - sg));
+    if (x < -80.f) {
+      const float e = expf(0.5f * x);
+      return ((1.0f + x) * e) * e;
+    }
+    const float e = expf(-x), sg = 1.0f / (1.0f + e);
+    return sg * (1.0f + x * (e * sg));  // 1 - sg = e * sg, without the cancellation of 1 - sg for large x
   }
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
+  return 0.5f * erfcf(x * -0.70710678118654752440f) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
 }
 __global__ void act_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, int64_t n,
                            int mode) {
@@ -25,7 +38,8 @@ __global__ void act_kernel(const float* __restrict__ x, const float* __restrict_
   out[i] = dy ? dy[i] * act_grad(x[i], mode) : act_fwd(x[i], mode);
 }
 
-// dtable[cls][j] += sum over kept rows of that class (row order), dnull[j] = sum over dropped rows; one thread per column
+// dtable[cls][j] += sum over kept rows of that class (row order), dnull[j] = sum over dropped rows; one thread per column.
+// A kept row whose id lies outside the table (its forward row is NaN, embed.hip) adds to no table row.
 __global__ void class_embed_bwd_kernel(const float* __restrict__ d, const int64_t* __restrict__ classes,
                                        const unsigned char* __restrict__ keep, float* __restrict__ dtable,
                                        float* __restrict__ dnull, int B, int D, int num_classes) {
@@ -35,10 +49,11 @@ __global__ void class_embed_bwd_kernel(const float* __restrict__ d, const int64_
   float dn = 0.f;
   for (int b = 0; b < B; ++b) {
     const float v = d[(size_t)b * D + j];
-    if (keep[b])
-      dtable[(size_t)classes[b] * D + j] += v;
-    else
+    const int64_t c = classes[b];
+    if (!keep[b])
       dn += v;
+    else if (c >= 0 && c < num_classes)
+      dtable[(size_t)c * D + j] += v;
   }
   dnull[j] = dn;
 }

@@ -569,9 +569,11 @@ def test_user_loop_loss_backward_and_torch_optimizer(golden_dir):
 
 def test_conv_wgrad_dynamic_range(ops):
     """the fp16-piece weight-gradient kernel under the conditions its block scaling exists for: gradient magnitudes
-    from 1e-9 to 1e+3 and activations from 1e-4 to 1e+4 varying over decades ACROSS tiles (the running maxima rise and
-    fall along a workgroup's item range, the accumulators get rescaled), whole tiles of exact zeros (masked loss), and a
-    few isolated huge values — against fp64 autograd, error measured against the result's own scale"""
+    from 1e-9 to 1e+3 and activations from 1e-4 to 1e+4 varying over decades ACROSS tiles, whole tiles of exact zeros
+    (masked loss), and a few isolated huge values — against fp64 autograd, error measured against the result's own
+    scale.  At this shape every workgroup owns ONE item (72 items over 72 splits), so this covers the per-item block
+    scaling and the split-to-split reduction; the rescale along a workgroup's item range is tested in
+    test_gpu_wgrad_splits.py::test_wgrad_dynamic_range_along_a_split."""
     B, H, W, C, Co = 3, 32, 48, 64, 64
     g = torch.Generator().manual_seed(910)
     dy = torch.randn((B, Co, H, W), generator=g)
