@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: sampled images/sec of the DGM denoising hot path (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], README inference config at 128x128): CFG Unet dim=64,
@@ -20,7 +20,13 @@ N > 1 without a torchrun environment: this process only LAUNCHES (it never touch
 with the child's code — the counterpart of the reference's N hand-started processes (README:14,
 DGM/dgm_sample.py:13-18).
 
-Prints ONE JSON line on rank 0, including
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up, warms up, times the K steps,
+writes its outputs (--dump-outputs) and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, `config`, ...).  With --full it also measures and checks the rest, all of it outside the timed region
+(each leg can be left out with its --no-* flag):
+  phases       the per-rank / per-phase diagnosis of an N-rank line
+  variants     dedup_dropped_rows (the opt-in row de-duplication, timed in extra steps) and, N = 1, exact_fp32 (a fresh
+               child process under DMH_CONV3_VARIANT=6); config.measured_rel_error: the canonical conv against fp64
   roofline     the dominant kernel (stride-1 3x3 conv, conv_f16x3_kernel<3,3,1,0,...>: implicit GEMM on the fp16
                matrix cores, every fp32 product carried by three fp16 MFMAs under block scaling).
                achieved = ALGORITHMIC FLOPs (2*9*Cin*Cout*H*W*B) of its launches / their HIP-event
@@ -181,7 +187,7 @@ def exact_fp32_variant(args, timeout=420):
     throughput trade of `config.arithmetic` buys on THIS box.  -> dict for the JSON line (an 'error' entry when it failed)."""
     cmd = [sys.executable, os.path.abspath(__file__), '--steps', '3', '--warmup', '1', '--bs', str(args.bs), '--s_step',
            str(args.s_step), '--image_size', str(args.image_size), '--dim', str(args.dim), '--cfg-mode', args.cfg_mode,
-           '--no-variants', '--no-traffic', '--no-cpu-baseline', '--no-roofline', '--no-phases'] + (
+           '--full', '--no-variants', '--no-traffic', '--no-cpu-baseline', '--no-roofline', '--no-phases'] + (
                ['--no-graph'] if args.no_graph else [])
     try:
         rc, out, err = run_child(cmd, timeout, env=child_env(DMH_CONV3_VARIANT='6'), cwd=ROOT)
@@ -431,16 +437,17 @@ def plumbing_only(args):
     tb = time.perf_counter()
     D.broadcast_module_(diffusion, src=0)
     dist.barrier()
-    broadcast_first_ms = (time.perf_counter() - tb) * 1e3
-    tb = time.perf_counter()
-    D.broadcast_module_(diffusion, src=0)
-    dist.barrier()
-    broadcast_ms = (time.perf_counter() - tb) * 1e3
+    broadcast_first_ms = broadcast_ms = (time.perf_counter() - tb) * 1e3
+    if not args.no_phases:
+        tb = time.perf_counter()
+        D.broadcast_module_(diffusion, src=0)
+        dist.barrier()
+        broadcast_ms = (time.perf_counter() - tb) * 1e3
     digest = torch.tensor([float(sum(p.double().sum() for p in diffusion.state_dict().values()))], dtype=torch.float64)
     lo, hi = D.shard_bounds(args.bs * world, rank, world)
     imgs = torch.arange(lo, hi, dtype=torch.uint8).reshape(-1, 1, 1, 1).expand(-1, 6, 4, 4).contiguous()
     homos = torch.arange(lo, hi, dtype=torch.float64).reshape(-1, 1, 1).expand(-1, 3, 3).contiguous()
-    smi_before = smi_sample(0)
+    smi_before = smi_sample(0) if not args.no_phases else None
     dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -449,12 +456,14 @@ def plumbing_only(args):
     dist.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    tg = time.perf_counter()
-    D.gather_records(imgs, homos, dst=0)
-    phases = assemble_phases({'rank': rank, 'ms_per_step': elapsed_local / max(args.steps, 1) * 1e3, 'local_ms': 0.0,
-                              'gather_ms': (time.perf_counter() - tg) * 1e3, 'smi_before': smi_before,
-                              'smi_after': smi_sample(0), 'host': socket.gethostname(), 'device': str(device)},
-                             rank, world, broadcast_ms, broadcast_first_ms)
+    phases = None
+    if not args.no_phases:
+        tg = time.perf_counter()
+        D.gather_records(imgs, homos, dst=0)
+        phases = assemble_phases({'rank': rank, 'ms_per_step': elapsed_local / max(args.steps, 1) * 1e3, 'local_ms': 0.0,
+                                  'gather_ms': (time.perf_counter() - tg) * 1e3, 'smi_before': smi_before,
+                                  'smi_after': smi_sample(0), 'host': socket.gethostname(), 'device': str(device)},
+                                 rank, world, broadcast_ms, broadcast_first_ms)
     ranks = torch.ones(1)
     dist.all_reduce(ranks)
     dmin, dmax = digest.clone(), digest.clone()
@@ -463,15 +472,19 @@ def plumbing_only(args):
     if rank == 0:
         ok = (gi[:, 0, 0, 0].tolist() == list(range(args.bs * world)) and gh[:, 0, 0].tolist() ==
               [float(i) for i in range(args.bs * world)] and float(dmin) == float(dmax))
-        print(json.dumps({'metric': 'plumbing only (no sampling: CPU test mode)', 'value': None, 'n_gpus': world,
-                          'steps': args.steps, 'warmup': args.warmup, 'rccl_ranks': int(ranks.item()),
-                          'backend': dist.get_backend(), 'plumbing_only': True, 'records_in_rank_order': bool(ok),
-                          'global_batch': args.bs * world, 'elapsed_s': float(t.item()), 'phases': phases}), flush=True)
+        res = {'metric': 'plumbing only (no sampling: CPU test mode)', 'value': None, 'n_gpus': world,
+               'steps': args.steps, 'warmup': args.warmup, 'rccl_ranks': int(ranks.item()),
+               'backend': dist.get_backend(), 'plumbing_only': True, 'records_in_rank_order': bool(ok),
+               'global_batch': args.bs * world, 'elapsed_s': float(t.item())}
+        if phases is not None:
+            res['phases'] = phases
+        print(json.dumps(res), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
+    """the command line; without --full every leg beside the headline is switched off (the --no-* flags then say so)"""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
@@ -480,21 +493,27 @@ def main():
     ap.add_argument('--s_step', type=int, default=32)
     ap.add_argument('--image_size', type=int, default=128)
     ap.add_argument('--dim', type=int, default=64)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline, outside the timed region: `phases`, '
+                         '`roofline` (with its rocprofv3 traffic passes), `variants` (dedup_dropped_rows, exact_fp32), '
+                         '`config.measured_rel_error` and `cpu_baseline`; the --no-* flags below leave out one of them. '
+                         'Without it a run sets up, warms up, times the steps, dumps its outputs if asked and prints the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
     ap.add_argument('--cfg-mode', default='streams', choices=['batched', 'streams'])
     ap.add_argument('--stream-splits', type=int, default=1, help="row sub-batches per CFG pass in 'streams' mode")
     ap.add_argument('--no-graph', action='store_true', help="launch every kernel from Python instead of replaying the "
                     "HIP graph of the sampling loop (cfg.GaussianDiffusion.hip_graph)")
-    ap.add_argument('--no-roofline', action='store_true', help='skip the extra untimed step that carries the HIP events')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the extra untimed step that carries the '
+                    'HIP events')
     ap.add_argument('--no-traffic', action='store_true',
-                    help='quote roofline.traffic from the committed PMC profile instead of measuring it (two child runs under '
-                         'rocprofv3 --pmc, ~40 s, after the timed region; single-GPU runs only)')
+                    help='with --full: quote roofline.traffic from the committed PMC profile instead of measuring it (two '
+                         'child runs under rocprofv3 --pmc, ~40 s, after the timed region; single-GPU runs only)')
     ap.add_argument('--no-variants', action='store_true',
-                    help='skip the extra steps (after the timed region) that time cfg.Unet.dedup_dropped_rows and report it '
-                         'under "variants" (the headline `value` never includes it)')
+                    help='with --full: skip the extra steps (after the timed region) that time cfg.Unet.dedup_dropped_rows '
+                         'and the exact-fp32 child run, reported under "variants" (the headline `value` never includes them)')
     ap.add_argument('--no-phases', action='store_true',
-                    help='skip the per-rank / per-phase diagnosis (weight payload, local step, gather, rocm-smi samples: all '
-                         'outside the timed region) reported under "phases"')
+                    help='with --full: skip the per-rank / per-phase diagnosis (weight payload, local step, gather, rocm-smi '
+                         'samples: all outside the timed region) reported under "phases"')
     ap.add_argument('--dedup', action='store_true',
                     help='development / profiling: run the TIMED loop itself with cfg.Unet.dedup_dropped_rows (the line is then '
                          'labelled as that variant and is not the headline)')
@@ -507,11 +526,18 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned (rank 0\'s gathered records: '
                          'imgs as float32, homos as float64) to DIR/<name>.npy, at most 64 MB in all (see dump_outputs)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     if args.dump_outputs and (args.workload != 'sample' or args.device != 'cuda'):
         ap.error('--dump-outputs covers the sampling workload on the GPU only')
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_traffic = args.no_variants = args.no_phases = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.cpu_probe:
         return cpu_probe(args)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -550,16 +576,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the weight payload (scatter + all-gather, distributed.py), timed twice: the first call also builds the communicator
+    # the weight payload (scatter + all-gather, distributed.py); for `phases` timed twice: the first call also builds the
+    # communicator
     fence()
     tb = time.perf_counter()
     D.broadcast_module_(diffusion, src=0)
     fence()
-    broadcast_first_ms = (time.perf_counter() - tb) * 1e3
-    tb = time.perf_counter()
-    D.broadcast_module_(diffusion, src=0)
-    fence()
-    broadcast_ms = (time.perf_counter() - tb) * 1e3
+    broadcast_first_ms = broadcast_ms = (time.perf_counter() - tb) * 1e3
+    if not args.no_phases:
+        tb = time.perf_counter()
+        D.broadcast_module_(diffusion, src=0)
+        fence()
+        broadcast_ms = (time.perf_counter() - tb) * 1e3
     # (ONE denoise step is captured and replayed s_step times: any depth, the 250-step stress configuration included)
     use_graph = not args.no_graph
     diffusion.hip_graph = use_graph
@@ -703,12 +731,14 @@ def main():
         # the measured error of this process's conv arithmetic on the canonical shape (fp64 host reference), and — beside the
         # headline, from a fresh child process — what the exact-fp32 kernels deliver on this box, with their error
         own = 'f16x3' if os.environ.get('DMH_CONV3_VARIANT', '9') == '9' else f"DMH_CONV3_VARIANT={os.environ['DMH_CONV3_VARIANT']}"
-        try:
-            res['config']['measured_rel_error'] = {own: conv_error(args.image_size, device)}
-        except Exception as e:
-            res['config']['measured_rel_error'] = {'error': f'{type(e).__name__}: {str(e)[:160]}'}
-        res['config']['measured_rel_error_note'] = ('max |y - y64| / max |y64| of one row of the canonical weight-standardised 3x3 conv '
-                                                    '64->64 at image_size^2 on N(0,1) input against an fp64 host convolution')
+        if args.full:
+            try:
+                res['config']['measured_rel_error'] = {own: conv_error(args.image_size, device)}
+            except Exception as e:
+                res['config']['measured_rel_error'] = {'error': f'{type(e).__name__}: {str(e)[:160]}'}
+            res['config']['measured_rel_error_note'] = ('max |y - y64| / max |y64| of one row of the canonical weight-standardised '
+                                                        '3x3 conv 64->64 at image_size^2 on N(0,1) input against an fp64 host '
+                                                        'convolution')
         if not args.no_variants and world == 1 and own == 'f16x3':
             torch.cuda.synchronize()
             ex = exact_fp32_variant(args)

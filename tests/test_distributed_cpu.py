@@ -212,10 +212,11 @@ def test_bench_launches_its_own_ranks():
     assert len(lines) == 1, r.stdout
     res = json.loads(lines[0])
     assert res['n_gpus'] == 2 and res['rccl_ranks'] == 2 and res['records_in_rank_order'] and res['global_batch'] == 6
+    assert 'phases' not in res                            # (a plain run: the diagnosis is --full's)
     # ... and the 8 ranks of BASELINE configs[2]
     env8 = dict(env, OMP_NUM_THREADS='1')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--device', 'cpu', '--bs', '3',
-                        '--steps', '2', '--warmup', '0'], capture_output=True, text=True, env=env8, timeout=600)
+                        '--steps', '2', '--warmup', '0', '--full'], capture_output=True, text=True, env=env8, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     assert res['n_gpus'] == 8 and res['rccl_ranks'] == 8 and res['records_in_rank_order'] and res['global_batch'] == 24

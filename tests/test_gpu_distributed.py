@@ -252,8 +252,8 @@ def test_bench_ranks_on_one_gpu(ranks, extra):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(DMH_DIST_BACKEND='gloo', DMH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--s_step', '4', '--steps', '2',
-                        '--warmup', '1', '--no-cpu-baseline', '--no-roofline'] + extra, capture_output=True, text=True, env=env,
-                       cwd=root, timeout=1200)
+                        '--warmup', '1', '--full', '--no-cpu-baseline', '--no-roofline'] + extra, capture_output=True, text=True,
+                       env=env, cwd=root, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -282,8 +282,8 @@ def test_bench_single_gpu_line_carries_exact_fp32_and_measured_error():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.pop('DMH_CONV3_VARIANT', None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--s_step', '4', '--steps', '2', '--warmup', '1', '--bs', '3',
-                        '--dim', '8', '--image_size', '32', '--no-cpu-baseline', '--no-roofline'], capture_output=True, text=True,
-                       env=env, cwd=root, timeout=1200)
+                        '--dim', '8', '--image_size', '32', '--full', '--no-cpu-baseline', '--no-roofline'], capture_output=True,
+                       text=True, env=env, cwd=root, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     ex = d['variants']['exact_fp32']
@@ -295,6 +295,30 @@ def test_bench_single_gpu_line_carries_exact_fp32_and_measured_error():
     ph = d['phases']
     assert len(ph['per_rank_ms']) == 1 and ph['per_rank_ms'][0] <= d['ms_per_step'] * 1.001 and ph['local_ms'][0] > 0
     assert isinstance(ph['smi'][0]['after'], dict)
+
+
+def test_bench_plain_line_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full (a small model): ONE line with the headline fields and none of the legs --full adds
+    (phases, variants, roofline, cpu_baseline, config.measured_rel_error); --dump-outputs still writes the last timed
+    step's records"""
+    import json
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--s_step', '4', '--steps', '2',
+                        '--warmup', '1', '--bs', '3', '--dim', '8', '--image_size', '32', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, env=env, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d['metric'].startswith('sampled images/sec (32x32, s_step=4)') and d['unit'] == 'images/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f32' and (d['steps'], d['warmup']) == (2, 1)
+    assert d['ms_per_step'] > 0 and abs(d['value'] - 3 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    assert not {'phases', 'variants', 'roofline', 'cpu_baseline'} & set(d), sorted(d)
+    assert 'measured_rel_error' not in d['config']
+    imgs, homos = np.load(str(tmp_path / 'imgs.npy')), np.load(str(tmp_path / 'homos.npy'))
+    assert imgs.shape == (3, 6, 32, 32) and homos.shape == (3, 3, 3)
 
 
 def test_train_bench_four_ranks_on_one_gpu():

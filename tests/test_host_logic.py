@@ -316,3 +316,21 @@ def test_bench_dump_outputs_writes_the_records_within_the_budget(tmp_path, monke
     assert np.array_equal(a1, a2) and np.array_equal(rows, np.load(str(tmp_path / 's2' / 'imgs_rows.npy')))
     assert np.array_equal(a1, imgs.numpy()[rows.astype(np.int64)].astype(np.float32))
     assert sum(os.path.getsize(str(tmp_path / 's1' / f)) for f in os.listdir(str(tmp_path / 's1'))) < 4096 + bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_plain_run_leaves_every_other_leg_to_full():
+    """bench.py without --full runs the headline alone: every leg beside it (phases, roofline and its traffic passes,
+    variants, cpu_baseline) is off whatever --no-* flags say; with --full each is on unless its own --no-* flag is given"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod4', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = ('no_cpu_baseline', 'no_roofline', 'no_traffic', 'no_variants', 'no_phases')
+    for argv in (['--gpus', '1', '--steps', '5', '--warmup', '2'], ['--no-roofline'], ['--dump-outputs', 'd']):
+        a = bench.parse_args(argv)
+        assert not a.full and all(getattr(a, k) for k in legs), argv
+    a = bench.parse_args(['--steps', '5', '--warmup', '2', '--full'])
+    assert a.full and not any(getattr(a, k) for k in legs) and (a.steps, a.warmup) == (5, 2)
+    a = bench.parse_args(['--full', '--no-roofline', '--no-cpu-baseline'])
+    assert a.no_roofline and a.no_cpu_baseline and not (a.no_traffic or a.no_variants or a.no_phases)

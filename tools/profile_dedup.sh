@@ -5,9 +5,9 @@ O=$R/gpurun_out/r5d
 rm -rf $O && mkdir -p $O
 stats() { find $1 -name '*kernel_stats.csv' | head -1; }
 for mode in streams batched; do
-  python3 $R/bench.py --steps 4 --warmup 1 --cfg-mode $mode --no-cpu-baseline --no-roofline > $O/bench_$mode.json 2> $O/bench_$mode.err
+  python3 $R/bench.py --steps 4 --warmup 1 --cfg-mode $mode --full --no-cpu-baseline --no-roofline > $O/bench_$mode.json 2> $O/bench_$mode.err
 done
-python3 $R/bench.py --steps 4 --warmup 1 --cfg-mode streams --stream-splits 2 --no-cpu-baseline --no-roofline > $O/bench_streams_split2.json 2>> $O/bench_streams.err
+python3 $R/bench.py --steps 4 --warmup 1 --cfg-mode streams --stream-splits 2 --full --no-cpu-baseline --no-roofline > $O/bench_streams_split2.json 2>> $O/bench_streams.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dd -o s -- python3 $R/bench.py --steps 2 --warmup 1 --dedup --no-variants --no-cpu-baseline --no-roofline > $O/dedup_streams.log 2>&1
 cp "$(stats $O/dd)" $O/bench_dedup_streams_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ff -o s -- python3 $R/bench.py --steps 2 --warmup 1 --no-variants --no-cpu-baseline --no-roofline > $O/full_streams.log 2>&1
