@@ -7,8 +7,6 @@ so scripts written against the reference (``DGM/dgm_sample.py:28-38``) run
 unchanged — but every tensor value is produced by the gfx950 kernels of
 libdmhomo_hip.so (see ``engine.py``).  There is no CPU path.
 """
-from collections import OrderedDict, namedtuple
-
 import torch
 from torch import nn
 
@@ -16,101 +14,8 @@ from . import _params as P
 from . import ops
 from ._lib import DmhStep
 from .engine import UnetEngine
+from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
 from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
-
-ModelPrediction = namedtuple('ModelPrediction', ['pred_noise', 'pred_x_start'])
-
-
-def exists(x):
-    return x is not None
-
-
-def default(val, d):
-    if exists(val):
-        return val
-    return d() if callable(d) else d
-
-
-def extract(a, t, x_shape):
-    """D3, CFG:472-475: a.gather(-1, t) shaped (b, 1, ..., 1) (integer indexing: tensor plumbing)."""
-    b, *_ = t.shape
-    out = a.gather(-1, t)
-    return out.reshape(b, *((1,) * (len(x_shape) - 1)))
-
-
-class DeviceRng:
-    """The noise source of the samplers, drawn in the reference's call order (CFG:679 randn(shape), CFG:90
-    zeros(B).uniform_(0,1), CFG:703 randn_like).
-
-    Default: torch's generator of the target device — the reference's own behaviour: row b of a draw depends on how many
-    rows the process holds and on the process's seed.
-    After ``key_by_sample(seed, sample_ids)``: every value is a pure function of (seed, GLOBAL sample id, draw index,
-    element) (``dmh_rng_indexed``: Philox4x32-10 + Box-Muller; the draw index lives in device memory and advances with
-    every launch, also inside a replayed HIP graph) — a batch sharded over N ranks, each keyed with its own slice of the
-    sample ids, reproduces the single-GPU batch row for row, bit for bit."""
-
-    def __init__(self):
-        self.sample_ids = None           # (B,) int64 device tensor once keyed
-        self.state = None                # (4,) int64 device tensor: seed, draw index, tickets, reserved
-
-    def key_by_sample(self, seed, sample_ids, device=None):
-        """sample_ids: the GLOBAL indices of this process's rows (``range(lo, hi)`` of distributed.shard_bounds), in row
-        order.  Re-keying with the same number of rows on the same device keeps the tensors' storage (a captured graph
-        stays valid) and restarts the draw index at 0."""
-        ids = torch.as_tensor(list(sample_ids), dtype=torch.int64)
-        device = torch.device(device) if device is not None else (self.sample_ids.device if self.sample_ids is not None
-                                                                 else torch.device('cuda', torch.cuda.current_device()))
-        state = torch.tensor([int(seed), 0, 0, 0], dtype=torch.int64)
-        if self.sample_ids is not None and self.sample_ids.shape == ids.shape and self.sample_ids.device == device:
-            self.sample_ids.copy_(ids)
-            self.state.copy_(state)
-        else:
-            self.sample_ids, self.state = ids.to(device), state.to(device)
-        return self
-
-    def unkey(self):
-        self.sample_ids = self.state = None
-        return self
-
-    @property
-    def keyed(self):
-        return self.sample_ids is not None
-
-    def graph_key(self):
-        """what a captured launch of this generator bakes in"""
-        return None if not self.keyed else (self.sample_ids.data_ptr(), self.state.data_ptr(), int(self.sample_ids.shape[0]))
-
-    def snapshot(self, device):
-        """state to put back with ``restore`` (the eager warm-up in front of a graph capture must not consume draws)"""
-        if self.keyed:
-            return ('indexed', self.state.clone())
-        return ('stream', torch.cuda.get_rng_state(device))
-
-    def restore(self, snap, device):
-        if snap[0] == 'indexed':
-            self.state.copy_(snap[1])
-        else:
-            torch.cuda.set_rng_state(snap[1], device)
-
-    def ids_for(self, n):
-        """the sample ids of a draw with n rows: all of them, or — a short last batch of a loader that keeps it, as the
-        reference's DataLoader does (DDP:1746-1752) — the first n (a view: same storage, so a captured graph keyed on the
-        full-size batch is not disturbed)"""
-        n = int(n)
-        if n > self.sample_ids.shape[0]:
-            raise ValueError(f'the generator is keyed for {self.sample_ids.shape[0]} rows, a draw asks for {n}: '
-                             f'key_by_sample with the ids of this batch first')
-        return self.sample_ids if n == self.sample_ids.shape[0] else self.sample_ids[:n]
-
-    def randn(self, shape, device):
-        if self.keyed:
-            return ops.rng_indexed(shape, self.ids_for(shape[0]), self.state, 0)
-        return torch.randn(tuple(shape), device=device)
-
-    def uniform(self, n, device):
-        if self.keyed:
-            return ops.rng_indexed((n,), self.ids_for(n), self.state, 1)
-        return torch.zeros((n,), device=device).float().uniform_(0, 1)
 
 
 # development knob (same-box A/Bs): '0' = the replayed step computes its embeddings and (scale, shift) rows per step
@@ -288,84 +193,6 @@ def _bind_forward(forward, args, kwargs):
     return a['x'], a['time'], a['classes'], a['rgb_flow'], a['mask']
 
 
-class ScheduleHost:
-    """host mirrors of the schedule buffers: the reference indexes device buffers with python ints and does
-    0-dim fp32 tensor arithmetic on them (CFG:697-701); here the same ops run on CPU copies and the results
-    enter the sampler kernel as scalars."""
-
-    _HOST_NAMES = ('alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'sqrt_alphas_cumprod',
-                   'sqrt_one_minus_alphas_cumprod', 'posterior_mean_coef1', 'posterior_mean_coef2',
-                   'posterior_log_variance_clipped')
-
-    def _host(self):
-        """CPU copies of the schedule buffers, cached per buffer version (a device -> host copy per sampling call would
-        also be illegal inside a HIP-graph capture)."""
-        sig = tuple((getattr(self, n).data_ptr(), getattr(self, n)._version) for n in self._HOST_NAMES)
-        cache = self.__dict__.get('_host_cache')
-        if cache is None or cache[0] != sig:
-            cache = (sig, {n: getattr(self, n).detach().cpu() for n in self._HOST_NAMES})
-            self.__dict__['_host_cache'] = cache
-        return cache[1]
-
-    # ---- D4 / D7: the affine combinations of CFG:586-608 [DDP:584-611] with a timestep per row
-    def _at(self, name, t, neg=False):
-        a = getattr(self, name)
-        return (-a if neg else a).gather(-1, t.to(torch.int64)).contiguous()
-
-    def predict_start_from_noise(self, x_t, t, noise):
-        """CFG:586-588: extract(sqrt_recip_ac) * x_t - extract(sqrt_recipm1_ac) * noise."""
-        return ops.rows_lincomb(x_t, self._at('sqrt_recip_alphas_cumprod', t), noise,
-                                self._at('sqrt_recipm1_alphas_cumprod', t, neg=True))
-
-    def predict_noise_from_start(self, x_t, t, x0):
-        """CFG:590-594: (extract(sqrt_recip_ac) * x_t - x0) / extract(sqrt_recipm1_ac)."""
-        minus_one = torch.full((x_t.shape[0],), -1., device=x_t.device, dtype=torch.float32)
-        return ops.rows_lincomb(x_t, self._at('sqrt_recip_alphas_cumprod', t), x0, minus_one,
-                                div=self._at('sqrt_recipm1_alphas_cumprod', t))
-
-    def predict_v(self, x_start, t, noise):
-        """CFG:596-598: extract(sqrt_ac) * noise - extract(sqrt_1m_ac) * x_start."""
-        return ops.rows_lincomb(noise, self._at('sqrt_alphas_cumprod', t), x_start,
-                                self._at('sqrt_one_minus_alphas_cumprod', t, neg=True))
-
-    def predict_start_from_v(self, x_t, t, v):
-        """CFG:600-601: extract(sqrt_ac) * x_t - extract(sqrt_1m_ac) * v."""
-        return ops.rows_lincomb(x_t, self._at('sqrt_alphas_cumprod', t), v,
-                                self._at('sqrt_one_minus_alphas_cumprod', t, neg=True))
-
-    def q_posterior(self, x_start, x_t, t):
-        """CFG:603-608: (posterior mean, variance, clipped log variance), the last two shaped (b, 1, 1, 1)."""
-        mean = ops.rows_lincomb(x_start, self._at('posterior_mean_coef1', t), x_t, self._at('posterior_mean_coef2', t))
-        return (mean, extract(self.posterior_variance, t, x_t.shape),
-                extract(self.posterior_log_variance_clipped, t, x_t.shape))
-
-    def _predictions_per_row(self, model_output, x, t, clip_x_start):
-        """the objective branch of model_predictions (CFG:614-628) for a batch whose rows sit at different timesteps"""
-        one = torch.ones((x.shape[0],), device=x.device, dtype=torch.float32)
-        clip = (lambda v: ops.rows_lincomb(v, one, clamp=True)) if clip_x_start else (lambda v: v)
-        if self.objective == 'pred_noise':
-            pred_noise = model_output
-            x_start = clip(self.predict_start_from_noise(x, t, pred_noise))
-        elif self.objective == 'pred_x0':
-            x_start = clip(model_output)
-            pred_noise = self.predict_noise_from_start(x, t, x_start)
-        else:                                                # pred_v
-            x_start = clip(self.predict_start_from_v(x, t, model_output))
-            pred_noise = self.predict_noise_from_start(x, t, x_start)
-        return ModelPrediction(pred_noise, x_start)
-
-    def _ddim_coef(self, host, time, time_next):
-        """sqrt(alpha_next), c, sigma in the reference's op order, CFG:697-701."""
-        alpha = host['alphas_cumprod'][time]
-        alpha_next = host['alphas_cumprod'][time_next]
-        sigma = self.ddim_sampling_eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-        # For a first jump from t=T-1 (alpha ~ 2e-9) to alpha_next >~ 1e-2 (s_step <= 8) the radicand is pure fp32
-        # cancellation noise of +-6e-8 and the reference yields c = NaN on hosts whose sqrt rounds the other way
-        # (seen: 999 -> 499).  Clamping at 0 changes nothing where the reference is finite.
-        c = (1 - alpha_next - sigma ** 2).clamp(min=0).sqrt()
-        return float(alpha_next.sqrt()), float(c), float(sigma)
-
-
 class GaussianDiffusion(nn.Module, ScheduleHost):
     """CFG:498-842 — sampling side on the GPU kernels; buffers and their names as the reference."""
 
@@ -399,23 +226,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def rng(self, value):
         self.model.rng = value
 
-    def _step(self, host, t, mode, cond_scale, clip, c=(0., 0., 0.)):
-        return DmhStep(objective=ops.OBJECTIVE[self.objective], clip=int(bool(clip)), mode=mode,
-                       cond_scale=float(cond_scale),
-                       sqrt_recip_ac=float(host['sqrt_recip_alphas_cumprod'][t]),
-                       sqrt_recipm1_ac=float(host['sqrt_recipm1_alphas_cumprod'][t]),
-                       sqrt_ac=float(host['sqrt_alphas_cumprod'][t]),
-                       sqrt_1m_ac=float(host['sqrt_one_minus_alphas_cumprod'][t]),
-                       c0=float(c[0]), c1=float(c[1]), c2=float(c[2]))
-
-    @staticmethod
-    def _uniform_time(t):
-        """python int when every row shares the timestep (always true while sampling), else None"""
-        t0 = int(t[0])
-        if t.numel() > 1 and not bool((t == t0).all()):
-            return None
-        return t0
-
     def _network(self, x, t, classes, rgb_flow, mask, cond_scale):
         """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null"""
         if cond_scale == 1:
@@ -434,7 +244,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                                 cond_scale=float(cond_scale), sqrt_recip_ac=1., sqrt_recipm1_ac=1.)
                 cond, _, _ = ops.sampler_step(blend, cond, null, null, None, want_x_start=False, keep=computed)
             return self._predictions_per_row(cond, x.contiguous(), t, clip_x_start)
-        step = self._step(host, t0, ops.MODE_LAST, cond_scale, clip_x_start)
+        step = self._step(host, t0, ops.MODE_LAST, clip_x_start, cond_scale=cond_scale)
         _, x_start, pred_noise = ops.sampler_step(step, cond, null, x.contiguous(), None, True, True, keep=computed)
         return ModelPrediction(pred_noise, x_start)
 
@@ -470,18 +280,12 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests."""
         batch, device = shape[0], self.betas.device
-        host = self._host()
+        steps = self._ddim_steps(clip_denoised, cond_scale)
         img = self.rng.randn(shape, device).contiguous()
-        for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
+        for time, step, draws in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
-            if time_next < 0:
-                step = self._step(host, time, ops.MODE_LAST, cond_scale, clip_denoised)
-                noise = None
-            else:
-                step = self._step(host, time, ops.MODE_DDIM, cond_scale, clip_denoised,
-                                  self._ddim_coef(host, time, time_next))
-                noise = self.rng.randn(shape, device).contiguous()
+            noise = self.rng.randn(shape, device).contiguous() if draws else None
             img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
             if trace is not None:
                 trace.append({'time': time, 'x_start': x_start, 'img': img})
@@ -497,21 +301,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                         '(CFG:656 vs CFG:719-720); use sampling_timesteps < timesteps (DDIM), or the unconditional '
                         'denoising_diffusion_pytorch.GaussianDiffusion for ancestral sampling')
 
-    # hip_graph = True: ONE denoise step of the sampling loop of CFG:683-707 (every kernel of it, on however many HIP
-    # streams cfg_mode uses) is captured per (shapes, cond_scale, weight version, schedule) into a HIP graph and replayed
-    # S times: the step's coefficients and its timestep come from device tables that a cursor kernel at the end of the
-    # step advances (dmh_sampler_seek), so the same ~660-node graph serves every step and any S (s_step = 250 included),
-    # the capture costs one step, and the host queues replay k + 1 while replay k runs.  The last step (no noise draw,
-    # img = x_start, CFG:693-695) is a second graph in the same memory pool.  Same kernels, same order, same device RNG
-    # stream (the Philox offsets are graph inputs): results are bitwise those of the eager path, the capturing call
-    # included (the RNG state is restored after the eager warm-up).  Off by default; bench.py switches it on.
-    # Captured steps are kept in a small least-recently-used cache (``graph_cache_size`` entries, each with its own graphs,
-    # memory pool and static buffers): a job that alternates batch shapes — the short last batch of every epoch of
-    # scripts/dgm_sample.py's loader, two samplers sharing one model — captures each shape once, not once per alternation.
-    hip_graph = False
-    graph_cache_size = 4
-    graph_captures = 0                   # captures made by this object so far (tests count them)
-
     @torch.no_grad()
     def sample(self, classes, rgb_flow, flow, mask, cond_scale=3.):
         """CFG:713-720."""
@@ -524,91 +313,49 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         rgb_flow = ops.affine(rgb_flow.to(torch.float32), 2., -1.)      # normalize_to_neg_one_to_one, CFG:716
         return self.ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale)
 
-    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale):
-        eng = self.model._engine
-        eng.ensure_prepared()
-        host = self._host()                                  # (host mirrors cached before any capture)
-        device = classes.device
-        clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
-        # everything that is baked into the captured launches or into the step tables
-        key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), self.model.cfg_mode, int(self.model.stream_splits),
-               bool(self.model.dedup_dropped_rows), bool(self.model.share_first_conv), float(self.model.cond_drop_prob), eng._sig, self.sampling_timesteps,
-               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.__dict__['_host_cache'][0],
-               str(device), self.rng.graph_key())
-        cache = self.__dict__.setdefault('_graph_states', OrderedDict())
-        st = cache.get(key)
-        if st is not None:
-            cache.move_to_end(key)
-        else:
-            steps, times = [], []
-            for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
-                if time_next < 0:
-                    steps.append(self._step(host, time, ops.MODE_LAST, cond_scale, clip))
-                else:
-                    steps.append(self._step(host, time, ops.MODE_DDIM, cond_scale, clip,
-                                            self._ddim_coef(host, time, time_next)))
-                times.append(time)
-            assert steps[-1].mode == ops.MODE_LAST and all(s_.mode == ops.MODE_DDIM for s_ in steps[:-1])
-            table, tt, cursor, cur = ops.step_table(steps, times, device)
-            ins = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
-            st = {'key': key, 'ins': ins, 'table': table, 'times': tt, 'cursor': cursor, 'cur': cur, 'nsteps': len(steps),
-                  'rf': torch.empty_like(ins[1]), 'img': torch.zeros(shape, device=device),
-                  'tcond': torch.zeros((shape[0],), device=device, dtype=torch.long)}
+    def _graph_tables(self, cond_scale, clip=True):
+        """host side of the replayed loop: (steps, times, draws), entry k = the DmhStep, timestep and 'draws noise' flag
+        _ddim_sample passes at its k-th step."""
+        times, steps, draws = map(list, zip(*self._ddim_steps(clip, cond_scale)))
+        return steps, times, draws
 
+    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale):
+        """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times"""
+        m, eng, device = self.model, self.model._engine, classes.device
+        clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
+        # everything besides weights, schedule and device that is baked into the captured launches or the step tables
+        key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
+               bool(m.dedup_dropped_rows), bool(m.share_first_conv), float(m.cond_drop_prob), self.sampling_timesteps,
+               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key())
+
+        def buffers(st, times, draws):
+            ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
+            st['rf'] = torch.empty_like(ins[1])
+            ops.affine(ins[1], 2., -1., out=st['rf'])        # (the warm-up's input)
             # the embedding side of the network depends on (step, class, keep bit) only: tables, made once per capture
             if SS_TABLES:
                 T_tab, C_tab = eng.ss_tables(times)
-                st['ss_tab'] = (T_tab, C_tab, cursor)
+                st['ss_tab'] = (T_tab, C_tab, st['cursor'])
 
             def mid():                                       # one denoise step of CFG:684-707, in place on st['img']
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
                 noise = self.rng.randn(shape, device).contiguous()
-                ops.sampler_step_dev(cur, cond, null, st['img'], noise, out=st['img'], keep=computed)
-                ops.sampler_seek(cursor, -1, table, tt, cur, st['tcond'])
+                ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=st['img'], keep=computed)
+                ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
 
             def last():                                      # CFG:693-695 + unnormalize, CFG:709
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
-                x0 = ops.sampler_step_dev(cur, cond, null, st['img'], None, keep=computed)
+                x0 = ops.sampler_step_dev(st['cur'], cond, null, st['img'], None, keep=computed)
                 return ops.affine(x0, 0.5, 0.5)
-            # eager warm-up of both bodies on a side stream (first-launch work: LDS attributes, side streams), as
-            # torch.cuda.graphs asks for; the device RNG state is put back afterwards, so the capturing call consumes
-            # exactly what an eager sample() would
-            rng_state = self.rng.snapshot(device)
-            ops.affine(ins[1], 2., -1., out=st['rf'])
-            ops.sampler_seek(cursor, 0, table, tt, cur, st['tcond'])
-            side = torch.cuda.Stream(device=device)
-            side.wait_stream(torch.cuda.current_stream())
-            self.model.__dict__['_ss_tab'] = st.get('ss_tab')         # (read by Unet._run while the step bodies run)
-            try:
-                with torch.cuda.stream(side):
-                    mid()
-                    ops.sampler_seek(cursor, len(steps) - 1, table, tt, cur, st['tcond'])   # last() runs on the last entry
-                    last()
-                torch.cuda.current_stream().wait_stream(side)
-                g_mid = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_mid, capture_error_mode='thread_local'):
-                    mid()
-                g_last = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_last, pool=g_mid.pool(), capture_error_mode='thread_local'):
-                    st['out'] = last()
-            finally:
-                self.model.__dict__.pop('_ss_tab', None)
-            self.rng.restore(rng_state, device)
-            st['graph'], st['graph_last'] = g_mid, g_last
-            cache[key] = st
-            self.graph_captures = self.graph_captures + 1
-            while len(cache) > max(int(self.graph_cache_size), 1):
-                cache.popitem(last=False)                    # least recently used: its graphs, pool and buffers go with it
-        self.__dict__['_graph_state'] = st                   # (the entry this call replays)
-        for dst, src in zip(st['ins'], (classes, rgb_flow, mask)):
-            dst.copy_(src)
-        ops.affine(st['ins'][1], 2., -1., out=st['rf'])      # normalize_to_neg_one_to_one, CFG:716
-        st['img'].copy_(self.rng.randn(shape, device))       # CFG:679
-        ops.sampler_seek(st['cursor'], 0, st['table'], st['times'], st['cur'], st['tcond'])
-        for _ in range(st['nsteps'] - 1):
-            st['graph'].replay()
-        st['graph_last'].replay()
-        return st['out'].clone(), mask, flow
+            return mid, last
+
+        def fill(st):
+            for dst, src in zip(st['ins'], (classes, rgb_flow, mask)):
+                dst.copy_(src)
+            ops.affine(st['ins'][1], 2., -1., out=st['rf'])  # normalize_to_neg_one_to_one, CFG:716
+            st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
+        img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip), buffers, fill)
+        return img, mask, flow
 
     @torch.no_grad()
     def interpolate(self, x1, x2, t=None, lam=0.5):

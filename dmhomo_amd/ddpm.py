@@ -7,7 +7,6 @@ helpers DDP:913-988,1262-1299,1471-1486,1558-1678 and the ``Trainer`` surface DD
 All tensor values come from libdmhomo_hip.so; there is no CPU path.
 """
 import os
-from collections import OrderedDict
 from pathlib import Path
 
 import numpy as np
@@ -16,9 +15,8 @@ from torch import nn
 
 from . import _params as P
 from . import ops
-from ._lib import DmhStep
-from .cfg import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
 from .engine import UnetEngine
+from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
 from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
 
 __version__ = '0.1.0'
@@ -89,14 +87,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             self.register_buffer(name, val)
         self.rng = DeviceRng()
 
-    def _step(self, host, t, mode, clip, c=(0., 0., 0.)):
-        return DmhStep(objective=ops.OBJECTIVE[self.objective], clip=int(bool(clip)), mode=mode, cond_scale=1.,
-                       sqrt_recip_ac=float(host['sqrt_recip_alphas_cumprod'][t]),
-                       sqrt_recipm1_ac=float(host['sqrt_recipm1_alphas_cumprod'][t]),
-                       sqrt_ac=float(host['sqrt_alphas_cumprod'][t]),
-                       sqrt_1m_ac=float(host['sqrt_one_minus_alphas_cumprod'][t]),
-                       c0=float(c[0]), c1=float(c[1]), c2=float(c[2]))
-
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False):
         """DDP:613-634 (one timestep per batch, as every sampler uses it: one fused pass; a timestep per row: row by row)."""
         out = self.model(x, t, x_self_cond)
@@ -106,11 +96,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         step = self._step(self._host(), t0, ops.MODE_LAST, clip_x_start)
         _, x_start, pred_noise = ops.sampler_step(step, out, None, x.contiguous(), None, True, True)
         return ModelPrediction(pred_noise, x_start)
-
-    @staticmethod
-    def _uniform_time(t):
-        t0 = int(t[0])
-        return None if (t.numel() > 1 and not bool((t == t0).all())) else t0
 
     def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True):
         """DDP:636-645: (posterior mean, variance, clipped log variance, x_start) of one ancestral step."""
@@ -160,35 +145,18 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         if self._graphed():
             return self._sample_graphed(shape, 'ddim', bool(clip_denoised))
         batch, device = shape[0], self.betas.device
-        host = self._host()
+        steps = self._ddim_steps(clip_denoised)
         img = self.rng.randn(shape, device).contiguous()
         x_start = None
-        for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
+        for time, step, draws in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             self_cond = x_start if self.self_condition else None
             out = self.model(img, time_cond, self_cond)
-            if time_next < 0:
-                step, noise = self._step(host, time, ops.MODE_LAST, clip_denoised), None
-            else:
-                step = self._step(host, time, ops.MODE_DDIM, clip_denoised, self._ddim_coef(host, time, time_next))
-                noise = self.rng.randn(shape, device).contiguous()
+            noise = self.rng.randn(shape, device).contiguous() if draws else None
             img, x_start, _ = ops.sampler_step(step, out, None, img, noise, True)
         img = ops.affine(img, 0.5, 0.5)
         ops.affine_tail_(img, img.shape[1] - 2, 2. * 512, -512.)   # (x*2-1)*512, DDP:728
         return img
-
-    # hip_graph = True (with the DeviceRng generator): p_sample_loop / ddim_sample capture ONE denoise step — the UNet on a static
-    # input buffer, dmh_sampler_step_ddp_dev, the cursor advance — into a HIP graph and replay it T (or S) times; the last step
-    # (no noise) + the unnormalise is a second graph in the same pool.  The step's coefficients, timestep and noise flag come from
-    # device tables (ops.step_table + a draws table) behind a cursor, as in classifier_free_guidance's replayed loop.  The fused
-    # step draws its noise from the keyed generator itself (or reads torch.randn's, drawn inside the graph) and writes the next
-    # step's NHWC input — cat(x_start, img) with self-conditioning — so the per-step randn and assemble_input passes are gone.
-    # Same arithmetic in the same order, same generator stream: results are bitwise the eager loop's, the capturing call
-    # included (the RNG state is restored after the eager warm-up).  Captures live in a small LRU keyed on everything they bake
-    # in; a miss first drops the entries of dead weights, schedules or devices.  Off by default; interpolate / p_sample stay eager.
-    hip_graph = False
-    graph_cache_size = 4
-    graph_captures = 0                   # captures made by this object so far (tests count them)
 
     def _graphed(self):
         return bool(self.hip_graph) and type(self.rng) is DeviceRng and self.betas.is_cuda
@@ -196,53 +164,35 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def _graph_tables(self, kind, clip=True):
         """host side of the replayed loop: (steps, times, draws), entry k = the DmhStep, timestep and 'draws noise' flag the
         eager p_sample_loop ('ddpm', T-1 .. 0) or ddim_sample ('ddim', ddim_pairs) passes at its k-th step."""
-        host = self._host()
-        steps, times, draws = [], [], []
         if kind == 'ddpm':
-            for t in reversed(range(0, self.num_timesteps)):
-                steps.append(self._ddpm_step(host, t, clip))
-                times.append(t)
-                draws.append(int(t > 0))                     # p_sample: no noise at t == 0 (DDP:659)
+            host = self._host()
+            entries = [(t, self._ddpm_step(host, t, clip), int(t > 0))   # p_sample: no noise at t == 0 (DDP:659)
+                       for t in reversed(range(0, self.num_timesteps))]
         elif kind == 'ddim':
-            for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
-                if time_next < 0:
-                    steps.append(self._step(host, time, ops.MODE_LAST, clip))
-                    draws.append(0)
-                else:
-                    steps.append(self._step(host, time, ops.MODE_DDIM, clip, self._ddim_coef(host, time, time_next)))
-                    draws.append(1)
-                times.append(time)
+            entries = self._ddim_steps(clip)
         else:
             raise ValueError(f'unknown sampling loop {kind!r}')
+        times, steps, draws = map(list, zip(*entries))
         return steps, times, draws
 
     def _sample_graphed(self, shape, kind, clip):
-        eng = self.model._engine
-        eng.ensure_prepared()
-        self._host()                                         # (host mirrors cached before any capture)
-        device, rng = self.betas.device, self.rng
+        """p_sample_loop / ddim_sample with hip_graph (ScheduleHost._replay_captured): one step of DDP:663-680 / 700-726
+        captured — the UNet on a static NHWC input, dmh_sampler_step_ddp_dev, the cursor advance — and replayed T or S times.
+        The fused step draws its noise from the keyed generator itself (or reads torch.randn's, drawn inside the graph), an
+        int32 draws table says which entries draw, and it writes the next step's padded input — cat(x_start, img) with
+        self-conditioning — so the per-step randn and assemble_input passes are gone.  interpolate / p_sample stay eager."""
+        eng, rng, device = self.model._engine, self.rng, self.betas.device
         sc = bool(self.self_condition)
         shape = tuple(int(v) for v in shape)
         B, Cc = shape[0], shape[1]
-        live = (eng._sig, self.__dict__['_host_cache'][0], str(device))
-        # everything that is baked into the captured launches or into the tables
+        # everything besides weights, schedule and device that is baked into the captured launches or the tables
         key = (shape, kind, self.num_timesteps, self.sampling_timesteps, float(self.ddim_sampling_eta), self.objective, clip, sc,
-               rng.graph_key()) + live
-        cache = self.__dict__.setdefault('_graph_states', OrderedDict())
-        st = cache.get(key)
-        if st is not None:
-            cache.move_to_end(key)
-        else:
-            for k in [k for k in cache if k[-3:] != live]:
-                del cache[k]                                 # captures of replaced weights / schedules / devices: never hit again
-            steps, times, draws = self._graph_tables(kind, clip)
-            table, tt, cursor, cur = ops.step_table(steps, times, device)
-            st = {'key': key, 'table': table, 'times': tt, 'cursor': cursor, 'cur': cur, 'nsteps': len(steps),
-                  'draws': torch.tensor(draws, dtype=torch.int32).to(device),
-                  'img': torch.zeros(shape, device=device),
-                  'xin': torch.zeros((B, shape[2], shape[3], eng.cin_pad), device=device),
-                  'tcond': torch.zeros((B,), device=device, dtype=torch.long),
-                  'zeros': torch.zeros(shape, device=device) if sc else None}
+               rng.graph_key())
+
+        def buffers(st, times, draws):
+            st['draws'] = torch.tensor(draws, dtype=torch.int32).to(device)
+            st['xin'] = torch.zeros((B, shape[2], shape[3], eng.cin_pad), device=device)
+            st['zeros'] = torch.zeros(shape, device=device) if sc else None
             keyed = rng.keyed
             ids = rng.ids_for(B) if keyed else None
             scale, shift = (2., -1.) if kind == 'ddpm' else (2. * 512, -512.)     # DDP:679 / DDP:728
@@ -254,50 +204,25 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             def mid():                                       # one step of DDP:663-680 / 700-726, in place on st['img']
                 out = network()
                 noise = None if keyed else rng.randn(shape, device)     # (torch's generator: its offsets are graph inputs)
-                ops.sampler_step_ddp_dev(cur, cursor, st['draws'], out, st['img'], noise, ids, rng.state if keyed else None,
-                                         xin=st['xin'], self_cond=sc)
-                ops.sampler_seek(cursor, -1, table, tt, cur, st['tcond'])
+                ops.sampler_step_ddp_dev(st['cur'], st['cursor'], st['draws'], out, st['img'], noise, ids,
+                                         rng.state if keyed else None, xin=st['xin'], self_cond=sc)
+                ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
 
             def last():                                      # the last step (no noise) + unnormalise, DDP:678-679 / 727-728
                 out = network()
-                ops.sampler_step_ddp_dev(cur, cursor, st['draws'], out, st['img'])
+                ops.sampler_step_ddp_dev(st['cur'], st['cursor'], st['draws'], out, st['img'])
                 img = ops.affine(st['img'], 0.5, 0.5)
                 ops.affine_tail_(img, Cc - 2, scale, shift)
                 return img
-            # eager warm-up of both bodies on a side stream, then the captures; the generator state is put back afterwards,
-            # so the capturing call consumes exactly what an eager call would
-            rng_state = rng.snapshot(device)
-            ops.sampler_seek(cursor, 0, table, tt, cur, st['tcond'])
-            side = torch.cuda.Stream(device=device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                mid()
-                ops.sampler_seek(cursor, len(steps) - 1, table, tt, cur, st['tcond'])   # last() runs on the last entry
-                last()
-            torch.cuda.current_stream().wait_stream(side)
-            g_mid = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_mid, capture_error_mode='thread_local'):
-                mid()
-            g_last = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_last, pool=g_mid.pool(), capture_error_mode='thread_local'):
-                st['out'] = last()
-            rng.restore(rng_state, device)
-            st['graph'], st['graph_last'], st['mid'] = g_mid, g_last, mid       # (mid: the step body, for tools that inspect it)
-            cache[key] = st
-            self.graph_captures = self.graph_captures + 1
-            while len(cache) > max(int(self.graph_cache_size), 1):
-                cache.popitem(last=False)                    # least recently used: its graphs, pool and buffers go with it
-        self.__dict__['_graph_state'] = st                   # (the entry this call replays)
-        st['img'].copy_(rng.randn(shape, device))            # DDP:668 / DDP:696
-        if sc:                                               # the first step's self-condition is zeros (DDP:410-411)
-            ops.assemble_input(st['zeros'], st['img'], None, cpad=st['xin'].shape[3], out=st['xin'])
-        else:
-            ops.assemble_input(st['img'], None, None, cpad=st['xin'].shape[3], out=st['xin'])
-        ops.sampler_seek(st['cursor'], 0, st['table'], st['times'], st['cur'], st['tcond'])
-        for _ in range(st['nsteps'] - 1):
-            st['graph'].replay()
-        st['graph_last'].replay()
-        return st['out'].clone()
+            return mid, last
+
+        def fill(st):
+            st['img'].copy_(rng.randn(shape, device))        # DDP:668 / DDP:696
+            if sc:                                           # the first step's self-condition is zeros (DDP:410-411)
+                ops.assemble_input(st['zeros'], st['img'], None, cpad=st['xin'].shape[3], out=st['xin'])
+            else:
+                ops.assemble_input(st['img'], None, None, cpad=st['xin'].shape[3], out=st['xin'])
+        return self._replay_captured(shape, device, key, lambda: self._graph_tables(kind, clip), buffers, fill)
 
     @torch.no_grad()
     def sample(self, batch_size=16):

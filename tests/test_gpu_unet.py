@@ -579,6 +579,8 @@ def test_sample_hip_graph_equals_eager(mode, S, size):
     assert not torch.equal(e_eta, eager5) or S == 1
     assert torch.equal(run(True, 5, rf01), e_eta)
     d.ddim_sampling_eta = 1.
+    cache = d.__dict__['_graph_states']
+    old = list(cache)
     with torch.no_grad():
         m.final_conv.bias.add_(0.25)                     # a new weight version: re-capture, not a stale replay
     e = run(False, 5, rf01)
@@ -586,6 +588,7 @@ def test_sample_hip_graph_equals_eager(mode, S, size):
     g_old = d.__dict__['_graph_state']['graph']
     assert torch.equal(run(True, 5, rf01), e)
     assert d.__dict__['_graph_state']['graph'] is not g_old
+    assert len(cache) == 1 and not any(k in cache for k in old)      # the old weights' captures are gone
     d.hip_graph = False
 
 

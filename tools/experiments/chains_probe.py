@@ -52,10 +52,10 @@ def chains(skew):
                 tc = torch.full((b,), time_, device=dev, dtype=torch.long)
                 cond, null = diffusion._network(imgs[ci], tc, classes[lo:hi], rf[lo:hi].contiguous(), mask[lo:hi].contiguous(), 3.)
                 if time_next < 0:
-                    step = diffusion._step(host, time_, ops.MODE_LAST, 3., True)
+                    step = diffusion._step(host, time_, ops.MODE_LAST, True, cond_scale=3.)
                     noise = None
                 else:
-                    step = diffusion._step(host, time_, ops.MODE_DDIM, 3., True, diffusion._ddim_coef(host, time_, time_next))
+                    step = diffusion._step(host, time_, ops.MODE_DDIM, True, diffusion._ddim_coef(host, time_, time_next), 3.)
                     noise = torch.randn_like(imgs[ci])
                 imgs[ci], _, _ = ops.sampler_step(step, cond, null, imgs[ci], noise, want_x_start=False)
     for st in streams:
