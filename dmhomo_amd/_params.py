@@ -10,7 +10,7 @@ Construction order follows the reference (CFG:333-401, DDP:338-406) so a given
 from torch import nn
 import torch
 
-HIDDEN = 128      # heads * dim_head = 4 * 32 (CFG:246-250)
+from .layout import HIDDEN      # heads * dim_head = 4 * 32 (CFG:246-250)
 
 
 class Holder(nn.Module):

@@ -3,7 +3,8 @@
 One ``UnetEngine`` serves both UNets of the reference (CFG = classifier_free_guidance.py,
 DDP = denoising_diffusion_pytorch.py); which one is decided by the parameters present.
 ``prepare`` folds weight standardisation (N1), repacks every conv into the tile-major
-layout of ``dmh_conv2d`` and transposes the small linears — once per weight version.
+layout of ``dmh_conv2d`` and transposes the small linears — once per weight version; the
+trunk's modules, their order and the skip stack come from ``layout.unet_layout``.
 ``forward_rows`` is the launch sequence of Unet.forward (CFG:412-466 / DDP:408-447):
 
   ResnetBlock  = conv3x3(+GN stats) -> gn_finalize(scale/shift) -> conv3x3 with fused
@@ -15,15 +16,13 @@ layout of ``dmh_conv2d`` and transposes the small linears — once per weight ve
   torch.cat    never materialises: convs take two source pointers
   Upsample     nearest x2 is index math inside the 3x3 gather
 """
-import math
 import os
 
 import torch
 
 from . import ops
+from .layout import ATTN_SCALE, HIDDEN, sinusoidal_freq, unet_layout
 
-HEADS, DIM_HEAD = 4, 32     # CFG:246,275
-ATTN_SCALE = DIM_HEAD ** -0.5
 # development knob: '0' = final_conv as its own launch over the stored output of the last ResnetBlock
 FUSED_FINAL = os.environ.get('DMH_FUSED_FINAL', '1') != '0'
 FUSED_LINATTN = os.environ.get('DMH_FUSED_LINATTN', '1') != '0'   # development knob: '0' = separate LayerNorm / to_qkv / core
@@ -35,10 +34,6 @@ class _Res:
 
 class _Attn:
     __slots__ = ('linear', 'ln_g', 'qkv', 'pla', 'plo', 'out', 'out_g')
-
-
-def _ceil4(c):
-    return (c + 3) // 4 * 4
 
 
 class UnetEngine:
@@ -66,25 +61,22 @@ class UnetEngine:
             raise RuntimeError('dmhomo_amd: the UNet must live on the GPU (call .cuda()); there is no CPU path')
         f32 = lambda k: sd[k].to(torch.float32).contiguous()
 
-        def conv(key, c0, c1=0, ws=False, stride=1, ups=0, bias=True):
-            w = f32(key + '.weight')
+        def conv(w, b, c0, c1=0, ws=False, stride=1, ups=0):
+            w = f32(w)
             if ws:
                 w = ops.ws_standardize(w)
-            b = f32(key + '.bias') if bias and (key + '.bias') in sd else None
-            return ops.PackedConv(w, b, c0, c1, stride, ups)
+            return ops.PackedConv(w, None if b is None else f32(b), c0, c1, stride, ups)
 
-        self.dim = sd['time_mlp.1.weight'].shape[1]
-        self.has_classes = 'classes_emb.weight' in sd
+        L = unet_layout(sd)
+        self.dim, self.has_classes = L.dim, L.has_classes
         emb_dim = sd['time_mlp.3.weight'].shape[0] * (2 if self.has_classes else 1)
         self.emb_dim = emb_dim
 
-        # N7 frequency table, computed as the reference does it on the host (CFG:167-169) — or the (learned / random) weights
-        # of RandomOrLearnedSinusoidalPosEmb (CFG:175-190), whose embedding is (t, sin, cos): time_mlp.1 then takes dim + 1
-        self.fourier_w = f32('time_mlp.0.weights') if 'time_mlp.0.weights' in sd else None
+        # N7 frequency table — or the (learned / random) weights of RandomOrLearnedSinusoidalPosEmb (CFG:175-190), whose
+        # embedding is (t, sin, cos): time_mlp.1 then takes dim + 1
+        self.fourier_w = f32('time_mlp.0.weights') if L.fourier else None
         if self.fourier_w is None:
-            half = self.dim // 2
-            f = math.log(10000) / (half - 1)
-            self.freq = torch.exp(torch.arange(half) * -f).to(dev)
+            self.freq = sinusoidal_freq(self.dim, dev)
         self.t_w1, self.t_b1 = f32('time_mlp.1.weight').t().contiguous(), f32('time_mlp.1.bias')
         self.t_w2, self.t_b2 = f32('time_mlp.3.weight').t().contiguous(), f32('time_mlp.3.bias')
         if self.has_classes:
@@ -94,99 +86,62 @@ class UnetEngine:
 
         # init conv: input channels padded to a multiple of 4 with zero weights
         w0 = f32('init_conv.weight')
-        self.cin, self.cin_pad = w0.shape[1], _ceil4(w0.shape[1])
+        self.cin, self.cin_pad = L.cin, L.cin_pad
         if self.cin_pad != self.cin:
             wp = torch.zeros((w0.shape[0], self.cin_pad, 7, 7), device=dev, dtype=torch.float32)
             wp[:, :self.cin] = w0
             w0 = wp
         self.init_conv = ops.PackedConv(w0, f32('init_conv.bias'), self.cin_pad)
 
-        mlp_w, mlp_b = [], []
-        self._ss_total = 0
-
-        def res(prefix, c0, c1=0):
-            r = _Res()
-            cout = sd[prefix + '.block1.proj.weight'].shape[0]
-            r.cout = cout
-            r.conv1 = conv(prefix + '.block1.proj', c0, c1, ws=True)
-            r.g1, r.b1 = f32(prefix + '.block1.norm.weight'), f32(prefix + '.block1.norm.bias')
-            r.conv2 = conv(prefix + '.block2.proj', cout, ws=True)
-            r.g2, r.b2 = f32(prefix + '.block2.norm.weight'), f32(prefix + '.block2.norm.bias')
-            r.res = conv(prefix + '.res_conv', c0, c1) if (prefix + '.res_conv.weight') in sd else None
-            r.ss_off = self._ss_total
-            mlp_w.append(f32(prefix + '.mlp.1.weight').t())
-            mlp_b.append(f32(prefix + '.mlp.1.bias'))
-            self._ss_total += 2 * cout
+        def res(n):
+            r, k = _Res(), n.keys
+            r.cout, r.ss_off = n.cout, n.ss_off
+            r.conv1 = conv(k['w1'], k['b1'], n.c0, n.c1, ws=True)
+            r.g1, r.b1 = f32(k['g1']), f32(k['be1'])
+            r.conv2 = conv(k['w2'], k['b2'], n.cout, ws=True)
+            r.g2, r.b2 = f32(k['g2']), f32(k['be2'])
+            r.res = conv(k['rw'], k['rb'], n.c0, n.c1) if 'rw' in k else None
             return r
 
-        def attn(prefix, c, linear):
-            a = _Attn()
-            a.linear = linear
-            a.ln_g = f32(prefix + '.fn.norm.g').reshape(-1).contiguous()
+        def attn(n):
+            a, k, c = _Attn(), n.keys, n.c0
+            a.linear = n.kind == 'linattn'
+            a.ln_g = f32(k['g']).reshape(-1).contiguous()
             a.pla = None
-            if linear and c % 32 == 0 and FUSED_LINATTN:
+            if a.linear and c % 32 == 0 and FUSED_LINATTN:
                 # LayerNorm + to_qkv + both attention passes in two kernels (ops.linear_attention_fused)
                 a.qkv = None
-                a.pla = ops.PackedLinAttn(f32(prefix + '.fn.fn.to_qkv.weight'))
+                a.pla = ops.PackedLinAttn(f32(k['qkv']))
             else:
-                a.qkv = conv(prefix + '.fn.fn.to_qkv', c, bias=False)
+                a.qkv = conv(k['qkv'], None, c)
+            a.out = conv(k['ow'], k['ob'], HIDDEN)
+            a.out_g = f32(k['og']).reshape(-1).contiguous() if a.linear else None
             a.plo = None
-            if linear:
-                a.out = conv(prefix + '.fn.fn.to_out.0', HEADS * DIM_HEAD)
-                a.out_g = f32(prefix + '.fn.fn.to_out.1.g').reshape(-1).contiguous()
-                if a.pla is not None and c == 64:   # to_out + LayerNorm + residual ride in the second fused pass
-                    a.plo = ops.PackedLinAttnOut(f32(prefix + '.fn.fn.to_out.0.weight'),
-                                                 f32(prefix + '.fn.fn.to_out.0.bias'), a.out_g)
-            else:
-                a.out = conv(prefix + '.fn.fn.to_out', HEADS * DIM_HEAD)
-                a.out_g = None
+            if a.pla is not None and c == 64:   # to_out + LayerNorm + residual ride in the second fused pass
+                a.plo = ops.PackedLinAttnOut(f32(k['ow']), f32(k['ob']), a.out_g)
             return a
 
-        ns = 1 + max(int(k.split('.')[1]) for k in sd if k.startswith('downs.'))
-        c = sd['init_conv.weight'].shape[0]
-        self.init_dim = c
-        self.downs, skip_c = [], []
-        for i in range(ns):
-            p = f'downs.{i}'
-            b1 = res(p + '.0', c)
-            skip_c.append(c)
-            b2 = res(p + '.1', c)
-            at = attn(p + '.2', c, True)
-            skip_c.append(c)
-            if (p + '.3.1.weight') in sd:                       # DDP: pixel-unshuffle + 1x1  == 2x2 / stride 2
-                w = f32(p + '.3.1.weight')
-                cout = w.shape[0]
-                w22 = w.reshape(cout, c, 2, 2).contiguous()     # channel index = c*4 + p1*2 + p2 (DDP:112)
-                down = ops.PackedConv(w22, f32(p + '.3.1.bias'), c, 0, stride=2)
+        self.blocks = []       # (node, _Res / _Attn / PackedConv), in trunk order
+        for n in L.nodes:
+            k = n.keys
+            if n.kind == 'res':
+                b = res(n)
+            elif n.kind in ('linattn', 'attn'):
+                b = attn(n)
+            elif n.kind == 'unshuffle':                        # pixel-unshuffle + 1x1  == 2x2 / stride 2
+                w22 = f32(k['w']).reshape(n.cout, n.c0, 2, 2).contiguous()     # channel index = c*4 + p1*2 + p2 (DDP:112)
+                b = ops.PackedConv(w22, f32(k['b']), n.c0, 0, stride=2)
             else:
-                k = sd[p + '.3.weight'].shape[-1]
-                down = conv(p + '.3', c, stride=2 if k == 4 else 1)
-            self.downs.append((b1, b2, at, down))
-            c = down.cout
-        self.mid1 = res('mid_block1', c)
-        self.mid_attn = attn('mid_attn', c, False)
-        self.mid2 = res('mid_block2', c)
-        self.ups = []
-        for i in range(ns):
-            p = f'ups.{i}'
-            s1 = skip_c.pop()
-            b1 = res(p + '.0', c, s1)
-            c = b1.cout
-            s2 = skip_c.pop()
-            b2 = res(p + '.1', c, s2)
-            c = b2.cout
-            at = attn(p + '.2', c, True)
-            if (p + '.3.1.weight') in sd:
-                up = conv(p + '.3.1', c, ups=1)
-            else:
-                up = conv(p + '.3', c)
-            self.ups.append((b1, b2, at, up))
-            c = up.cout
-        self.final_res = res('final_res_block', c, self.init_dim)
-        self.final_w = f32('final_conv.weight').reshape(sd['final_conv.weight'].shape[0], -1).contiguous()
+                b = conv(k['w'], k['b'], n.c0, stride=2 if n.kind == 'down4' else 1, ups=1 if n.kind == 'up3' else 0)
+            self.blocks.append((n, b))
+        # a res block followed by a fused LinearAttention hands it the LayerNorm statistics of its output
+        nxt = [b for _, b in self.blocks[1:]] + [None]
+        self._pixel_stats = [isinstance(a, _Attn) and a.pla is not None for a in nxt]
+        self.final_w = f32('final_conv.weight').reshape(L.out_dim, -1).contiguous()
         self.final_b = f32('final_conv.bias')
-        self.mlp_wt = torch.cat(mlp_w, dim=1).contiguous()       # (emb_dim, total)
-        self.mlp_b = torch.cat(mlp_b).contiguous()
+        res_nodes = [n for n in L.nodes if n.kind == 'res']
+        self.mlp_wt = torch.cat([f32(n.keys['mlp_w']).t() for n in res_nodes], dim=1).contiguous()     # (emb_dim, total)
+        self.mlp_b = torch.cat([f32(n.keys['mlp_b']) for n in res_nodes]).contiguous()
 
     # ------------------------------------------------------------------ blocks
     def _res(self, r, x0, x1, ss_all, pixel_stats=False, pre=None, final=None, keep_out=True, fin_out=None):
@@ -289,7 +244,7 @@ class UnetEngine:
         the same for every classifier-free-guidance pass of a sample and is computed once per sample (CFG:404 and :409 each
         run it; the rows are bitwise the same)."""
         self.ensure_prepared()
-        return ops.conv2d(self.downs[0][0].conv1, x0, None, want_stats=True)
+        return ops.conv2d(self.blocks[0][1].conv1, x0, None, want_stats=True)
 
     def trunk(self, x0, cond, taps=None, first=None, out=None, ss_all=None, rows=None):
         """everything after init_conv.  x0: stem() output with one row per row of ``cond``.
@@ -317,36 +272,29 @@ class UnetEngine:
         if ss_all is None:
             ss_all = ops.linear(cond, self.mlp_wt, self.mlp_b, act_in='silu')
         x = tap('init_conv', x0)
-        r = x
-        hs = []
-        for i, (b1, b2, at, down) in enumerate(self.downs):
-            x = tap(f'downs.{i}.0', self._res(b1, x, None, ss_all, pre=first if i == 0 else None))
-            hs.append(x)
-            x, pst = self._res(b2, x, None, ss_all, pixel_stats=True) if at.pla is not None else \
-                (self._res(b2, x, None, ss_all), None)
-            tap(f'downs.{i}.1', x)
-            x = tap(f'downs.{i}.2', self._attn(at, x, pst))
-            hs.append(x)
-            x = tap(f'downs.{i}.3', ops.conv2d(down, x, rows=rows))
-        x = tap('mid_block1', self._res(self.mid1, x, None, ss_all))
-        x = tap('mid_attn', self._attn(self.mid_attn, x))
-        x = tap('mid_block2', self._res(self.mid2, x, None, ss_all))
-        for i, (b1, b2, at, up) in enumerate(self.ups):
-            x = tap(f'ups.{i}.0', self._res(b1, x, hs.pop(), ss_all))
-            x, pst = self._res(b2, x, hs.pop(), ss_all, pixel_stats=True) if at.pla is not None else \
-                (self._res(b2, x, hs.pop(), ss_all), None)
-            tap(f'ups.{i}.1', x)
-            x = tap(f'ups.{i}.2', self._attn(at, x, pst))
-            x = tap(f'ups.{i}.3', ops.conv2d(up, x, rows=rows))
-        fr = self.final_res
-        if FUSED_FINAL and fr.res is not None and fr.res.k == 1 and fr.cout <= 64 and self.final_w.shape[0] <= 8 \
-                and ops.f16x3_default():
-            # final_conv (CFG:341, 471-472) rides on the last block's res_conv launch: the block's output is projected
-            # while it is still in registers, and only stored when a parity test taps it
-            x, y = self._res(fr, x, r, ss_all, final=(self.final_w, self.final_b), keep_out=taps is not None, fin_out=out)
-            tap('final_res_block', x)
-            return y
-        x = tap('final_res_block', self._res(fr, x, r, ss_all))
+        hs, pst, last = [x], None, len(self.blocks) - 1
+        for i, (n, b) in enumerate(self.blocks):
+            x1 = hs.pop() if n.c1 else None
+            if n.kind == 'res':
+                if i == last and FUSED_FINAL and b.res is not None and b.res.k == 1 and b.cout <= 64 \
+                        and self.final_w.shape[0] <= 8 and ops.f16x3_default():
+                    # final_conv (CFG:341, 471-472) rides on the last block's res_conv launch: the block's output is
+                    # projected while it is still in registers, and only stored when a parity test taps it
+                    x, y = self._res(b, x, x1, ss_all, final=(self.final_w, self.final_b), keep_out=taps is not None,
+                                     fin_out=out)
+                    tap(n.name, x)
+                    return y
+                if self._pixel_stats[i]:
+                    x, pst = self._res(b, x, x1, ss_all, pixel_stats=True)
+                else:
+                    x = self._res(b, x, x1, ss_all, pre=first if i == 0 else None)
+            elif n.kind in ('linattn', 'attn'):
+                x, pst = self._attn(b, x, pst), None
+            else:
+                x = ops.conv2d(b, x, rows=rows)
+            tap(n.name, x)
+            if n.push:
+                hs.append(x)
         y = ops.final_conv_nchw(x, self.final_w, self.final_b)
         if out is not None:
             out.copy_(y)

@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import ops
+from .layout import ATTN_SCALE, HIDDEN, sinusoidal_freq, unet_layout
 
 
 class ResnetBlockTrain:
@@ -100,10 +101,6 @@ class ResnetBlockTrain:
 # =====================================================================================================================
 # the whole conditional UNet (CFG:302-466): forward with saved activations + backward, on the HIP kernels
 # =====================================================================================================================
-HEADS, DIM_HEAD = 4, 32
-SCALE = DIM_HEAD ** -0.5
-
-
 class _LinAttn:
     """Residual(PreNorm(LinearAttention)) (CFG:96-103, 246-269) or, with linear=False, Residual(PreNorm(Attention))
     (CFG:273-296), on a stored qkv tensor."""
@@ -112,19 +109,19 @@ class _LinAttn:
         self.p, self.c, self.linear = p, c, linear
         self.fq = ops.PackedConv(p['qkv'], None, c, batch=batch)
         self.dq = ops.conv_dgrad_pack(p['qkv'], c, batch=batch)
-        self.fo = ops.PackedConv(p['ow'], p['ob'], HEADS * DIM_HEAD, batch=batch)
-        self.do = ops.conv_dgrad_pack(p['ow'], HEADS * DIM_HEAD, batch=batch)
+        self.fo = ops.PackedConv(p['ow'], p['ob'], HIDDEN, batch=batch)
+        self.do = ops.conv_dgrad_pack(p['ow'], HIDDEN, batch=batch)
 
     def forward(self, x):
         p = self.p
         xn = ops.chan_layernorm(x, p['g'])
         qkv = ops.conv2d(self.fq, xn)
         if self.linear:
-            o, core = ops.linear_attention_core_train(qkv, SCALE)
+            o, core = ops.linear_attention_core_train(qkv, ATTN_SCALE)
             y = ops.conv2d(self.fo, o)
             out = ops.chan_layernorm(y, p['og'], res=x)
         else:
-            o, core = ops.attention_core_train(qkv, SCALE)
+            o, core = ops.attention_core_train(qkv, ATTN_SCALE)
             y = None
             out = ops.conv2d(self.fo, o, res=x)
         return out, dict(x=x, xn=xn, o=o, y=y, core=core)
@@ -184,8 +181,8 @@ class UnetTrain:
     """forward (saving activations) and backward of classifier_free_guidance.Unet on the HIP kernels.
     ``module``: a dmhomo_amd.cfg.Unet (same parameter names as the reference), or a dmhomo_amd.ddpm.Unet (DDP:315-447:
     no class embedding — the embedding is time only — an optional self-conditioning input, the pixel-unshuffle
-    Downsample): ``forward_uncond`` then stands for ``forward``.  Gradients come back as {parameter name: tensor of the
-    parameter's shape}."""
+    Downsample): ``forward_uncond`` then stands for ``forward``.  The trunk's modules, their order and the skip stack come
+    from ``layout.unet_layout``.  Gradients come back as {parameter name: tensor of the parameter's shape}."""
 
     def __init__(self, module, groups=8):
         self.module, self.groups = module, groups
@@ -197,30 +194,27 @@ class UnetTrain:
         handful of small tensors derived from parameters by torch ops are re-derived.  Graph-capturable."""
         self.pack.run()
         sd = self.sd
-        self.mlp_w.copy_(torch.cat([sd[k + '.mlp.1.weight'] for k in self.mlp_names], 0))
-        self.mlp_b.copy_(torch.cat([sd[k + '.mlp.1.bias'] for k in self.mlp_names], 0))
+        self.mlp_w.copy_(torch.cat([sd[n.keys['mlp_w']] for n in self.res_nodes], 0))
+        self.mlp_b.copy_(torch.cat([sd[n.keys['mlp_b']] for n in self.res_nodes], 0))
 
     def refresh(self):
         """build everything from the module's parameters (first use, or after their storage moved)"""
         sd = {k: v.detach().to(torch.float32).contiguous() for k, v in self.module.named_parameters()}
         self.sd = sd
-        if 'time_mlp.0.weights' in sd or any(k.startswith('time_mlp.0.') for k, _ in self.module.named_buffers()):
+        self.layout = L = unet_layout(sd)
+        if L.fourier:
             # RandomOrLearnedSinusoidalPosEmb (CFG:175-190): its embedding is learned_dim + 1 wide and time_mlp.1 is sized for
             # THAT — the sinusoidal embedding below would feed it a wrong K silently.  No training entry point reaches such a
             # model (GaussianDiffusion refuses it, CFG:514-515); anything else that does gets told.
             raise NotImplementedError('training a Unet with learned_sinusoidal_cond / random_fourier_features is not supported: '
                                       'the training step has no gradient for RandomOrLearnedSinusoidalPosEmb.weights')
         self.pack = pb = ops.PackBatch()
-        self.uncond = 'classes_emb.weight' not in sd             # ddpm.Unet: time-only embedding
-        self.dim = sd['time_mlp.1.weight'].shape[1]
-        half = self.dim // 2
-        import math
-        if getattr(self, 'freq', None) is None:      # constant: built once (a host->device copy cannot sit in a HIP graph)
-            self.freq = torch.exp(torch.arange(half) * -(math.log(10000) / (half - 1))).to(sd['init_conv.weight'].device)
+        self.uncond = not L.has_classes                          # ddpm.Unet: time-only embedding
         dev = sd['init_conv.weight'].device
+        if getattr(self, 'freq', None) is None:      # constant: built once (a host->device copy cannot sit in a HIP graph)
+            self.freq = sinusoidal_freq(L.dim, dev)
         w0 = sd['init_conv.weight']
-        self.cin = w0.shape[1]
-        self.cin_pad = (self.cin + 3) // 4 * 4
+        self.cin, self.cin_pad = L.cin, L.cin_pad
         wp = torch.zeros((w0.shape[0], self.cin_pad, 7, 7), device=dev)
         cin = self.cin
 
@@ -229,73 +223,22 @@ class UnetTrain:
         pad_init()
         pb.pre.append(pad_init)
         self.init = _Conv(wp, sd['init_conv.bias'], 'init7', self.cin_pad, batch=pb)
-        self.blocks, self.ss_off, self.ss_total = {}, {}, 0
-
-        def res(prefix, c0, c1=0):
-            p = dict(w1=sd[prefix + '.block1.proj.weight'], b1=sd[prefix + '.block1.proj.bias'],
-                     g1=sd[prefix + '.block1.norm.weight'], be1=sd[prefix + '.block1.norm.bias'],
-                     w2=sd[prefix + '.block2.proj.weight'], b2=sd[prefix + '.block2.proj.bias'],
-                     g2=sd[prefix + '.block2.norm.weight'], be2=sd[prefix + '.block2.norm.bias'])
-            if (prefix + '.res_conv.weight') in sd:
-                p['rw'], p['rb'] = sd[prefix + '.res_conv.weight'], sd[prefix + '.res_conv.bias']
-            blk = ResnetBlockTrain(p, c0, c1, self.groups, batch=pb)
-            self.blocks[prefix] = blk
-            self.ss_off[prefix] = self.ss_total
-            self.ss_total += 2 * blk.cout
-            return blk
-
-        def attn(prefix, c, linear):
-            p = dict(g=sd[prefix + '.fn.norm.g'].reshape(-1).contiguous(), qkv=sd[prefix + '.fn.fn.to_qkv.weight'])
-            if linear:
-                p['ow'], p['ob'] = sd[prefix + '.fn.fn.to_out.0.weight'], sd[prefix + '.fn.fn.to_out.0.bias']
-                p['og'] = sd[prefix + '.fn.fn.to_out.1.g'].reshape(-1).contiguous()
+        self.blocks = {}
+        for n in L.nodes:
+            p = {role: sd[k] for role, k in n.keys.items()}
+            if n.kind == 'res':
+                self.blocks[n.name] = ResnetBlockTrain(p, n.c0, n.c1, self.groups, batch=pb)
+            elif n.kind in ('linattn', 'attn'):
+                p['g'] = p['g'].reshape(-1).contiguous()
+                if 'og' in p:
+                    p['og'] = p['og'].reshape(-1).contiguous()
+                self.blocks[n.name] = _LinAttn(p, n.c0, n.kind == 'linattn', batch=pb)
             else:
-                p['ow'], p['ob'] = sd[prefix + '.fn.fn.to_out.weight'], sd[prefix + '.fn.fn.to_out.bias']
-            a = _LinAttn(p, c, linear, batch=pb)
-            self.blocks[prefix] = a
-            return a
-
-        ns = 1 + max(int(k.split('.')[1]) for k in sd if k.startswith('downs.'))
-        self.ns = ns
-        c = w0.shape[0]
-        self.init_dim = c
-        skip_c = []
-        for i in range(ns):
-            pfx = f'downs.{i}'
-            b1 = res(pfx + '.0', c)
-            skip_c.append(c)
-            res(pfx + '.1', c)
-            attn(pfx + '.2', c, True)
-            skip_c.append(c)
-            if (pfx + '.3.1.weight') in sd:                       # DDP: pixel-unshuffle + 1x1
-                w = sd[pfx + '.3.1.weight']
-                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.1.bias'], 'unshuffle', c, batch=pb)
-            else:
-                w = sd[pfx + '.3.weight']
-                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.bias'], 'down4' if w.shape[-1] == 4 else 'same3', c, batch=pb)
-            c = w.shape[0]
-        res('mid_block1', c)
-        attn('mid_attn', c, False)
-        res('mid_block2', c)
-        for i in range(ns):
-            pfx = f'ups.{i}'
-            b1 = res(pfx + '.0', c, skip_c.pop())
-            c = b1.cout
-            b2 = res(pfx + '.1', c, skip_c.pop())
-            c = b2.cout
-            attn(pfx + '.2', c, True)
-            if (pfx + '.3.1.weight') in sd:
-                w = sd[pfx + '.3.1.weight']
-                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.1.bias'], 'up3', c, batch=pb)
-            else:
-                w = sd[pfx + '.3.weight']
-                self.blocks[pfx + '.3'] = _Conv(w, sd[pfx + '.3.bias'], 'same3', c, batch=pb)
-            c = w.shape[0]
-        res('final_res_block', c, self.init_dim)
-        self.mlp_names = [k for k in self.ss_off]          # creation order == offsets order
-        self.mlp_w = torch.cat([sd[k + '.mlp.1.weight'] for k in self.mlp_names], 0).contiguous()      # (total, emb)
-        self.mlp_b = torch.cat([sd[k + '.mlp.1.bias'] for k in self.mlp_names], 0).contiguous()
-        self.final_w = sd['final_conv.weight'].reshape(sd['final_conv.weight'].shape[0], -1).contiguous()   # (6, 64)
+                self.blocks[n.name] = _Conv(p['w'], p['b'], n.kind, n.c0, batch=pb)
+        self.res_nodes = [n for n in L.nodes if n.kind == 'res']       # in (scale, shift) column order
+        self.mlp_w = torch.cat([sd[n.keys['mlp_w']] for n in self.res_nodes], 0).contiguous()      # (total, emb)
+        self.mlp_b = torch.cat([sd[n.keys['mlp_b']] for n in self.res_nodes], 0).contiguous()
+        self.final_w = sd['final_conv.weight'].reshape(L.out_dim, -1).contiguous()   # (6, 64)
         assert self.final_w.data_ptr() == sd['final_conv.weight'].data_ptr()      # a view: follows the parameter
         pb.run()                                                 # the first fill of every image registered above
 
@@ -325,11 +268,9 @@ class UnetTrain:
     def _embed_backward(self, sv, dss_all, g):
         sd = self.sd
         dac, dw, db = ops.linear_backward(sv['ac'], self.mlp_w, dss_all)
-        off = 0
-        for k in self.mlp_names:
-            n2 = 2 * self.blocks[k].cout
-            g[k + '.mlp.1.weight'], g[k + '.mlp.1.bias'] = dw[off:off + n2].contiguous(), db[off:off + n2].contiguous()
-            off += n2
+        for n in self.res_nodes:
+            o, n2 = n.ss_off, 2 * n.cout
+            g[n.keys['mlp_w']], g[n.keys['mlp_b']] = dw[o:o + n2].contiguous(), db[o:o + n2].contiguous()
         dcond = ops.act(sv['cond'], 'silu', dy=dac)
         if self.uncond:
             da1, g['time_mlp.3.weight'], g['time_mlp.3.bias'] = ops.linear_backward(sv['a1'], sd['time_mlp.3.weight'], dcond)
@@ -374,55 +315,23 @@ class UnetTrain:
 
     def _trunk_forward(self, xin, ss_all, emb, taps=None):
         B = xin.shape[0]
-        T = []                                                   # tape: (kind, block name, saved)
-
-        def ss(prefix):
-            o = self.ss_off[prefix]
-            return ss_all[:, o:o + 2 * self.blocks[prefix].cout]
-
-        def run_res(prefix, x0, x1=None):
-            out, sv = self.blocks[prefix].forward(x0, x1, ss(prefix))
-            T.append(('res', prefix, sv))
-            if taps is not None:
-                taps[prefix] = out
-            return out
-
-        def run_attn(prefix, x0):
-            out, sv = self.blocks[prefix].forward(x0)
-            T.append(('attn', prefix, sv))
-            if taps is not None:
-                taps[prefix] = out
-            return out
-
-        def run_conv(prefix, x0):
-            out, sv = self.blocks[prefix].forward(x0)
-            T.append(('conv', prefix, sv))
-            if taps is not None:
-                taps[prefix] = out
-            return out
-
+        T = []                                                   # tape: (node, saved)
         h, _ = self.init.forward(xin)
         if taps is not None:
             taps['init_conv'] = h
             taps['ss_all'] = ss_all
-        r = h
-        hs = []
-        for i in range(self.ns):
-            h = run_res(f'downs.{i}.0', h)
-            hs.append(h)
-            h = run_res(f'downs.{i}.1', h)
-            h = run_attn(f'downs.{i}.2', h)
-            hs.append(h)
-            h = run_conv(f'downs.{i}.3', h)
-        h = run_res('mid_block1', h)
-        h = run_attn('mid_attn', h)
-        h = run_res('mid_block2', h)
-        for i in range(self.ns):
-            h = run_res(f'ups.{i}.0', h, hs.pop())
-            h = run_res(f'ups.{i}.1', h, hs.pop())
-            h = run_attn(f'ups.{i}.2', h)
-            h = run_conv(f'ups.{i}.3', h)
-        h = run_res('final_res_block', h, r)
+        hs = [h]                                                 # the skip stack (layout.py)
+        for n in self.layout.nodes:
+            blk = self.blocks[n.name]
+            if n.kind == 'res':
+                h, s = blk.forward(h, hs.pop() if n.c1 else None, ss_all[:, n.ss_off:n.ss_off + 2 * n.cout])
+            else:
+                h, s = blk.forward(h)
+            T.append((n, s))
+            if n.push:
+                hs.append(h)
+            if taps is not None:
+                taps[n.name] = h
         out = ops.final_conv_nchw(h, self.final_w, self.sd['final_conv.bias'])
         return out, dict(tape=T, emb=emb, xin=xin, hfinal=h, B=B)
 
@@ -454,80 +363,31 @@ class UnetTrain:
         db = ops._empty((no,), h)
         ops.call('dmh_sum_over_batch', ops.ptr(dbb), ops.ptr(db), B * nk, no)
         g['final_conv.bias'] = db
-        # ---- trunk, in reverse
-        dss_all = torch.zeros((B, self.ss_total), device=h.device, dtype=torch.float32)
-        names = {'w1': '.block1.proj.weight', 'b1': '.block1.proj.bias', 'g1': '.block1.norm.weight',
-                 'be1': '.block1.norm.bias', 'w2': '.block2.proj.weight', 'b2': '.block2.proj.bias',
-                 'g2': '.block2.norm.weight', 'be2': '.block2.norm.bias', 'rw': '.res_conv.weight', 'rb': '.res_conv.bias'}
-        idx = len(T)
-
-        def pop(kind):
-            nonlocal idx
-            idx -= 1
-            k, prefix, s = T[idx]
-            assert k == kind, (k, kind)
-            return prefix, s
-
-        def back_res(d):
-            prefix, s = pop('res')
-            blk = self.blocks[prefix]
-            dx, gg = blk.backward(s, d)
-            for k, v in gg.items():
-                if k == 'ss':
-                    o = self.ss_off[prefix]
-                    dss_all[:, o:o + 2 * blk.cout] = v
-                else:
-                    g[prefix + names[k]] = v.reshape(sd[prefix + names[k]].shape)
-            if blk.c1:
-                # (the skip half stays a channel-slice VIEW: its one consumer is the strided in-place add below)
-                return dx[..., :blk.c0].contiguous(), dx[..., blk.c0:]
-            return dx, None
-
-        def back_attn(d):
-            prefix, s = pop('attn')
-            a = self.blocks[prefix]
-            dx, gg = a.backward(s, d)
-            g[prefix + '.fn.norm.g'] = gg['g'].reshape(sd[prefix + '.fn.norm.g'].shape)
-            g[prefix + '.fn.fn.to_qkv.weight'] = gg['qkv']
-            if a.linear:
-                g[prefix + '.fn.fn.to_out.0.weight'], g[prefix + '.fn.fn.to_out.0.bias'] = gg['ow'], gg['ob']
-                g[prefix + '.fn.fn.to_out.1.g'] = gg['og'].reshape(sd[prefix + '.fn.fn.to_out.1.g'].shape)
+        # ---- trunk, in reverse: the gradients of the popped skip halves unwind the skip stack of the forward
+        dss_all = torch.zeros((B, self.layout.ss_total), device=h.device, dtype=torch.float32)
+        d, ds = dh, []
+        for n, s in reversed(T):
+            blk = self.blocks[n.name]
+            if n.push:                                           # its output was also pushed to the skip stack
+                d.add_(ds.pop())
+            if n.kind == 'res':
+                d, gg = blk.backward(s, d)
+                dss_all[:, n.ss_off:n.ss_off + 2 * n.cout] = gg.pop('ss')
+                if n.c1:
+                    # (the skip half stays a channel-slice VIEW: its one consumer is the strided in-place add)
+                    ds.append(d[..., n.c0:])
+                    d = d[..., :n.c0].contiguous()
+            elif n.kind in ('linattn', 'attn'):
+                d, gg = blk.backward(s, d)
             else:
-                g[prefix + '.fn.fn.to_out.weight'], g[prefix + '.fn.fn.to_out.bias'] = gg['ow'], gg['ob']
-            return dx
-
-        def back_conv(d):
-            prefix, x0 = pop('conv')
-            cv = self.blocks[prefix]
-            dx, dw_, db_ = cv.backward(x0, d)
-            wname = prefix + ('.1.weight' if cv.kind in ('up3', 'unshuffle') else '.weight')
-            g[wname], g[wname.replace('weight', 'bias')] = dw_, db_
-            return dx
-
-        d, dr = back_res(dh)                                     # final_res_block: input cat(x, r)
-        skip_grads = []                                          # gradients of the skip tensors, in pop order
-        for i in reversed(range(self.ns)):
-            d = back_conv(d)
-            d = back_attn(d)
-            d, ds2 = back_res(d)                                 # ups.i.1: cat(x, hs.pop())
-            d, ds1 = back_res(d)                                 # ups.i.0
-            skip_grads.append((ds1, ds2))
-        d, _ = back_res(d)                                       # mid_block2
-        d = back_attn(d)
-        d, _ = back_res(d)                                       # mid_block1
-        # forward pushed [downs.0: a, b, downs.1: a, b, ...]; ups.0 popped downs.(ns-1).b then .a, ...
-        for i in reversed(range(self.ns)):
-            ds1, ds2 = skip_grads[i]      # appended for ups.(ns-1), ..., ups.0; ups.j pops the pushes of downs.(ns-1-j)
-            d = back_conv(d)                                     # downs.i.3
-            d.add_(ds1)                                          # downs.i.2's output was also pushed to the skip stack
-            d = back_attn(d)
-            d, _ = back_res(d)                                   # downs.i.1
-            d.add_(ds2)                                          # downs.i.0's output was pushed too
-            d, _ = back_res(d)                                   # downs.i.0
-        d.add_(dr)                                               # r = init_conv output, also fed to final_res_block
+                d, gw, gb = blk.backward(s, d)
+                gg = dict(w=gw, b=gb)
+            for role, v in gg.items():
+                g[n.keys[role]] = v.reshape(sd[n.keys[role]].shape)
+        d.add_(ds.pop())                                         # r = init_conv output, also fed to final_res_block
+        assert not ds
         _, dw0, db0 = self.init.backward(sv['xin'], d, want_dx=False)
         g['init_conv.weight'], g['init_conv.bias'] = dw0[:, :self.cin].contiguous(), db0
-        assert idx == 0
         self._embed_backward(sv['emb'], dss_all, g)
         return g
 
