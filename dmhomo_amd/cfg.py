@@ -18,10 +18,6 @@ from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists,
 from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
 
 
-# development knob (same-box A/Bs): '0' = the replayed step computes its embeddings and (scale, shift) rows per step
-SS_TABLES = __import__('os').environ.get('DMH_SS_TABLES', '1') != '0'
-
-
 class Unet(nn.Module):
     """CFG:302-466.  ``forward`` launches the HIP program; parameters live in holders."""
 
@@ -117,9 +113,6 @@ class Unet(nn.Module):
     # matrix-bound kernels.  Results are identical (rows are independent, tests pin that bitwise).
     cfg_mode = 'batched'
     stream_splits = 1      # 'streams' mode: row sub-batches per pass, each on its own stream
-    # 'streams' mode: downs.0.0.block1.proj(stem output) once for both passes (bitwise the same rows); DMH_SHARE_FIRST_CONV=0
-    # is the development knob for same-box A/Bs
-    share_first_conv = __import__('os').environ.get('DMH_SHARE_FIRST_CONV', '1') != '0'
 
     def _cond_null(self, x, time, classes, rgb_flow, mask):
         """the two passes of CFG:404,409: (cond logits, null logits, computed).  computed is None — every row of the cond
@@ -138,7 +131,7 @@ class Unet(nn.Module):
             x0 = self._stem(x, rgb_flow, mask)                # once, on the main stream
             # ... and with it the first convolution behind it: the class embedding reaches a ResnetBlock only through the
             # scale / shift behind block1's GroupNorm, so downs.0.0.block1.proj(x0) is the same rows in both passes
-            first = self._engine.first_conv(x0) if self.share_first_conv else None
+            first = self._engine.first_conv(x0)
             cond_out = torch.empty((B, self.out_dim) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
             null_out = torch.empty_like(cond_out)
             bounds = [(i * B) // nsub for i in range(nsub + 1)]
@@ -325,7 +318,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
-               bool(m.dedup_dropped_rows), bool(m.share_first_conv), float(m.cond_drop_prob), self.sampling_timesteps,
+               bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
                self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key())
 
         def buffers(st, times, draws):
@@ -333,9 +326,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             st['rf'] = torch.empty_like(ins[1])
             ops.affine(ins[1], 2., -1., out=st['rf'])        # (the warm-up's input)
             # the embedding side of the network depends on (step, class, keep bit) only: tables, made once per capture
-            if SS_TABLES:
-                T_tab, C_tab = eng.ss_tables(times)
-                st['ss_tab'] = (T_tab, C_tab, st['cursor'])
+            T_tab, C_tab = eng.ss_tables(times)
+            st['ss_tab'] = (T_tab, C_tab, st['cursor'])
 
             def mid():                                       # one denoise step of CFG:684-707, in place on st['img']
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)

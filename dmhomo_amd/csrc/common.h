@@ -26,6 +26,21 @@ void dmh_set_error(const char* fmt, ...);
     }                                                                 \
   } while (0)
 
+// Raise the dynamic-LDS limit of a kernel that asks for more than 64 KB, once per launch site (a template launcher has one
+// site per instantiation) and process — a process drives one device.  A failed raise is reported here, by name, instead of
+// surfacing later as an unexplained launch error.
+#define DMH_RAISE_LDS_ONCE(kern, bytes, name)                                                                     \
+  do {                                                                                                            \
+    static bool raised_ = false;                                                                                  \
+    if (!raised_) {                                                                                               \
+      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes));              \
+      DMH_REQUIRE(e_ == hipSuccess, "%s: cannot raise the LDS limit to %d bytes: %s", name, (int)(bytes),         \
+                  hipGetErrorString(e_));                                                                         \
+      raised_ = true;                                                                                             \
+    }                                                                                                             \
+  } while (0)
+
 // size arguments of the pure host entry points (dmh_*_floats, dmh_conv_tiles, ...): a dimension outside (0, 2^20] — a caller's
 // uninitialised or overflowed int — is answered with -1 instead of entering the size arithmetic (found by the host-side
 // sanitizer build, make asan: a 2^30 channel count overflowed the int64 product)

@@ -306,19 +306,19 @@ static int launch_conv(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
   return DMH_OK;
 }
 
-// 3x3 tiling variants (development knob DMH_CONV3_VARIANT, read once; the default is the measured best):
-//   0..3  conv_igemm_kernel   (KC,TH) = (32,16) (16,16) (32,8) (16,8)
-//   6     conv_wino_kernel    Winograd F(2x2,3x3), 8x16 pixels x 64 cout per workgroup
-//   (7, 8: the bf16-piece direct / Winograd kernels of round 1 were measured slower than 9 on every shape and are no
-//    longer part of the library — DESIGN.md 3.1 keeps their numbers, the git history their sources)
-//   9     conv_f16x3_kernel   direct implicit GEMM on the fp16 matrix cores, block-scaled 2 x 3 fp16 pieces
+// 3x3 kernels (DMH_CONV3_VARIANT, read once; any other value means 9):
+//   0     conv_igemm_kernel   exact fp32 implicit GEMM, (KC,TH) = (32,16)
+//   6     conv_wino_kernel    exact fp32 Winograd F(2x2,3x3), 8x16 pixels x 64 cout per workgroup
+//   9     conv_f16x3_kernel   direct implicit GEMM on the fp16 matrix cores, block-scaled 2 x 3 fp16 pieces (the default)
+// (the other tilings and the bf16-piece kernels of round 1 were measured slower on every shape: DESIGN.md 3.1 keeps their
+//  numbers, the git history their sources)
 #define DMH_CONV3_DEFAULT 9
 static int conv3_variant() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DMH_CONV3_VARIANT");
     v = e ? atoi(e) : DMH_CONV3_DEFAULT;
-    if (v < 0 || v > 9 || v == 4 || v == 5 || v == 7 || v == 8) v = DMH_CONV3_DEFAULT;
+    if (v != 0 && v != 6) v = DMH_CONV3_DEFAULT;
   }
   return v;
 }
@@ -341,13 +341,8 @@ static int conv_out_dim(int in, int KH, int stride, int ups) {
 static int conv_th(int KH, int stride) {
   if (stride == 2) return 8;
   if (use_f16x3(KH, stride)) return 8;  // GroupNorm partials per 8 x 16 stat tile
-  if (KH == 3 && (conv3_variant() == 2 || conv3_variant() == 3 || conv3_variant() >= 5)) return 8;
+  if (KH == 3 && conv3_variant() == 6) return 8;
   return 16;
-}
-
-static int conv_kc_v(int KH, int stride) {
-  if (KH == 3 && stride == 1 && conv3_variant() != 0 && conv3_variant() != 2) return 16;
-  return conv_kc(KH, stride);
 }
 
 extern "C" int dmh_conv_tiles(int Hout, int Wout, int KH, int stride) {
@@ -361,7 +356,7 @@ extern "C" int64_t dmh_conv_pack_floats(int Cout, int C0, int C1, int KH, int KW
   if (use_f16x3(KH, (KH == 4 || KH == 2) ? 2 : 1) || use_f16x3_s2d(KH, 2, C0, C1))
     return dmh_f16x3_pack_floats(Cout, C0, C1, KH, KW);
   const int stride = (KH == 4 || KH == 2) ? 2 : 1;
-  const int KC = conv_kc_v(KH, stride);
+  const int KC = conv_kc(KH, stride);
   return (int64_t)cdiv(Cout, 64) * (cdiv(C0, KC) + cdiv(C1, KC)) * KH * KW * 64 * KC;
 }
 
@@ -374,7 +369,7 @@ extern "C" int dmh_pack_conv_weight(const float* w, float* wpack, int Cout, int 
   if (use_f16x3(KH, (KH == 4 || KH == 2) ? 2 : 1) || use_f16x3_s2d(KH, 2, C0, C1))
     return dmh_f16x3_pack(w, wpack, Cout, C0, C1, KH, KW, (hipStream_t)stream);
   const int stride = (KH == 4 || KH == 2) ? 2 : 1;
-  const int KC = conv_kc_v(KH, stride);
+  const int KC = conv_kc(KH, stride);
   const int nch0 = cdiv(C0, KC), nch1 = cdiv(C1, KC);
   const int64_t total = dmh_conv_pack_floats(Cout, C0, C1, KH, KW);
   hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -451,18 +446,12 @@ extern "C" int dmh_conv2d(const DmhConv* d, void* stream) {
       return launch_conv<1, 1, 1, 0, 32, 16, 16>(d, Hout, Wout, st);
     case 310:
       switch (conv3_variant()) {
-        case 1: return launch_conv<3, 3, 1, 0, 16, 16, 16, 3>(d, Hout, Wout, st);
-        case 2: return launch_conv<3, 3, 1, 0, 32, 8, 16, 3>(d, Hout, Wout, st);
-        case 3: return launch_conv<3, 3, 1, 0, 16, 8, 16, 4>(d, Hout, Wout, st);
         case 6: return dmh_wino_launch(d, Hout, Wout, st);
         case 9: return dmh_f16x3_launch(d, Hout, Wout, st);
         default: return launch_conv<3, 3, 1, 0, 32, 16, 16, 2>(d, Hout, Wout, st);
       }
     case 311:
       switch (conv3_variant()) {
-        case 1: return launch_conv<3, 3, 1, 1, 16, 16, 16, 3>(d, Hout, Wout, st);
-        case 2: return launch_conv<3, 3, 1, 1, 32, 8, 16, 3>(d, Hout, Wout, st);
-        case 3: return launch_conv<3, 3, 1, 1, 16, 8, 16, 4>(d, Hout, Wout, st);
         case 6: return dmh_wino_launch(d, Hout, Wout, st);
         case 9: return dmh_f16x3_launch(d, Hout, Wout, st);
         default: return launch_conv<3, 3, 1, 1, 32, 16, 16, 2>(d, Hout, Wout, st);

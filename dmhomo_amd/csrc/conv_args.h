@@ -25,8 +25,8 @@ struct ConvArgs {
   float pix_eps;
   int B, Hin, Win, C0, C1, Cout, Hout, Wout;
   int nch0, nch1, tilesX, tilesY;
-  int ablate;  // diagnostic builds only (DMH_STAMPS): bit 0 skips staging + transform, bit 1 skips the matrix phase
-  int xcd;     // 1: workgroup ids are re-dealt so that each XCD (id % 8) walks a contiguous run of tiles (DMH_CONV_XCD)
+  int ablate;  // diagnostic builds only (DMH_STAMPS): phases of conv_f16x3_kernel switched off bit by bit (conv_f16x3.hip)
+  int xcd;     // 1: workgroup ids are re-dealt so that each XCD (id % 8) walks a contiguous run of tiles; 2: cout tile innermost
   const int32_t* rows;  // DmhConv.rows: null, or the active row subset of this launch (common.h: dmh_rows_n / dmh_rows_phys)
 };
 
@@ -64,11 +64,7 @@ static inline ConvArgs fill_conv_args(const DmhConv* d, int Hout, int Wout, int 
   a.tilesX = cdiv(Wout, TW);
   a.tilesY = cdiv(Hout, TH);
   a.ablate = 0;
-  static const int xcd = [] {
-    const char* e = getenv("DMH_CONV_XCD");
-    return e ? atoi(e) : 1;
-  }();
-  a.xcd = xcd;
+  a.xcd = 1;  // workgroups dealt XCD by XCD; launch_f16x3 (conv_f16x3.hip) picks 2 at the deep levels
   a.rows = d->rows;
   return a;
 }

@@ -863,13 +863,7 @@ static int launch_f16x3(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
   if (const char* e = getenv("DMH_WINO_ABLATE")) a.ablate = atoi(e);
 #endif
   auto kern = conv_f16x3_kernel<KH, KW, S, UPS, TH, TW, WM, WN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       Cfg::LDS_BYTES);
-    DMH_REQUIRE(e == hipSuccess, "dmh_conv2d: cannot raise the LDS limit: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  DMH_RAISE_LDS_ONCE(kern, Cfg::LDS_BYTES, "dmh_conv2d(f16x3)");
   // round 6: at the levels with Hout <= 32 the cout tiles of one pixel tile are dealt to the SAME XCD (a.xcd = 2: the re-deal
   // walks the cout tile innermost; a function of the layer shape only, results bitwise unchanged).  Measured with a tight
   // A/B (10 alternating rounds, standard error 0.05 %): +0.24 % / +0.29 % / +0.29 % images/s on three boxes, all of it from
@@ -880,11 +874,7 @@ static int launch_f16x3(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
     const char* e = getenv("DMH_CONV_XCD_DEEP");
     return e ? atoi(e) : 32;
   }();
-  static const int xcd_deep_maxy = [] {   // (development knob: only launches with at most this many cout tiles)
-    const char* e = getenv("DMH_CONV_XCD_DEEP_MAXY");
-    return e ? atoi(e) : 1 << 20;
-  }();
-  if (a.xcd == 1 && xcd_deep > 0 && Hout <= xcd_deep && cdiv(a.Cout, 64 * WN) > 1 && cdiv(a.Cout, 64 * WN) <= xcd_deep_maxy) a.xcd = 2;
+  if (xcd_deep > 0 && Hout <= xcd_deep && cdiv(a.Cout, 64 * WN) > 1) a.xcd = 2;
   dim3 grid(a.tilesX * a.tilesY * a.B, cdiv(a.Cout, 64 * WN));
   hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::LDS_BYTES, st, a);
   DMH_CHECK_LAUNCH("dmh_conv2d(f16x3)");
@@ -931,13 +921,7 @@ int dmh_f16x3_launch_up2(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
   a.tilesY = cdiv(d->Hin, 4);
   a.oscale = d->wpack + f16x3_frag_floats(4 * d->Cout, a.C0, 0, 2, 2);
   auto kern = conv_f16x3_kernel<2, 2, 1, 3, 4, 16, 4, 1>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       Cfg::LDS_BYTES);
-    DMH_REQUIRE(e == hipSuccess, "dmh_conv2d: cannot raise the LDS limit: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  DMH_RAISE_LDS_ONCE(kern, Cfg::LDS_BYTES, "dmh_conv2d(f16x3 sub-pixel)");
   dim3 grid(a.tilesX * a.tilesY * a.B, cdiv(a.Cout, 64));
   hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::LDS_BYTES, st, a);
   DMH_CHECK_LAUNCH("dmh_conv2d(f16x3 sub-pixel)");
@@ -957,24 +941,14 @@ int dmh_f16x3_launch(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
     return launch_f16x3<7, 7, 1, 0, 16, 16, 4, 1>(d, Hout, Wout, st);
   }
   if (d->KH == 1) {
-    static int wide1 = -1;  // development knob
-    if (wide1 < 0) {
-      const char* e = getenv("DMH_F16_WIDE1");
-      wide1 = e ? atoi(e) : 1;
-    }
-    return (wide && wide1) ? launch_f16x3<1, 1, 1, 0, 8, 16, 2, 2>(d, Hout, Wout, st)
+    return wide ? launch_f16x3<1, 1, 1, 0, 8, 16, 2, 2>(d, Hout, Wout, st)
                 : launch_f16x3<1, 1, 1, 0, 16, 16, 4, 1>(d, Hout, Wout, st);
   }
   if (d->upsample2) {
     return wide ? launch_f16x3<3, 3, 1, 1, 8, 16, 2, 2>(d, Hout, Wout, st)
                 : launch_f16x3<3, 3, 1, 1, 16, 16, 4, 1>(d, Hout, Wout, st);
   }
-  static int wide3 = -1;  // development knob (DMH_F16_WIDE3=0: the 16x16x64 layout for every plain 3x3)
-  if (wide3 < 0) {
-    const char* e = getenv("DMH_F16_WIDE3");
-    wide3 = e ? atoi(e) : 1;
-  }
-  if (wide && wide3) return launch_f16x3<3, 3, 1, 0, 8, 16, 2, 2>(d, Hout, Wout, st);
+  if (wide) return launch_f16x3<3, 3, 1, 0, 8, 16, 2, 2>(d, Hout, Wout, st);
   // (the 16 x 16 layout keeps a load's source pixel relative to the tile in 16 bits: PACKPW in the kernel)
   DMH_REQUIRE(17 * (int64_t)d->Win + 17 < 65536, "dmh_conv2d: 3x3 with Cout %% 128 != 0 supports Win <= 3853 (got %d)", d->Win);
   return launch_f16x3<3, 3, 1, 0, 16, 16, 4, 1>(d, Hout, Wout, st);

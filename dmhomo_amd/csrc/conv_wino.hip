@@ -13,7 +13,6 @@
 // the output transform is register-local; results go through the shared float4 row epilogue
 // (+bias, +residual, GroupNorm partials).  Dual-source (fused torch.cat) and nearest-x2 upsampled
 // inputs are handled in the halo gather exactly as in conv.hip.
-#include <stdlib.h>
 
 #include "conv_args.h"
 
@@ -78,21 +77,6 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
   const int tile_in_sample = ty0 * p.tilesX + tx0;
   const int oy0 = ty0 * TH, ox0 = tx0 * TW;
 
-#ifdef DMH_STAMPS
-  // diagnostic build only (make stamps): per-wave cycle totals of each phase, written over this tile's stats slot
-  unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t_prev, t_now;
-#define STAMP(i)                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                             \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_now)::"memory"); \
-  __builtin_amdgcn_sched_barrier(0);                                             \
-  tk[i] += t_now - t_prev;                                                       \
-  t_prev = t_now;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_prev)::"memory");
-  const unsigned long long t_begin = t_prev;
-#else
-#define STAMP(i)
-#endif
 
   // ---- chunk-invariant staging state: 3 halo slots per thread (pixel, channel quad c4)
   const int c4 = tid & 3;
@@ -168,9 +152,6 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
 
   for (int ch = 0; ch < nchunks; ++ch) {
     // ---- 1. registers -> (prologue SiLU(a*x+b)) -> raw LDS tile
-#ifdef DMH_STAMPS
-    if (!(p.ablate & 1))
-#endif
     {
       const bool s1 = ch >= p.nch0;
       const bool pro = (p.in_coef != nullptr) && !s1;
@@ -201,17 +182,12 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
       bq[q][0] = ld4(wch + q * 1024 + wlane);
       bq[q][1] = ld4(wch + q * 1024 + 256 + wlane);
     }
-    STAMP(0)          // raw write (+ prologue)
     __syncthreads();  // raw published; every wave has also left the previous matrix phase (V is free)
-    STAMP(1)          // barrier 1
     // next chunk's halo (on the last chunk: a harmless re-load of itself — an UNCONDITIONAL issue lets hipcc
     // count vmcnt exactly instead of draining these loads at the first weight wait of the matrix phase)
     issue_chunk_loads(ch + 1 < nchunks ? ch + 1 : ch);
 
     // ---- 2. input transform V = B^T d B, two items per thread, packed fp32 adds
-#ifdef DMH_STAMPS
-    if (!(p.ablate & 1))
-#endif
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const float* pa = raw + rd_a[it];
@@ -230,14 +206,9 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
       stf4(vo + 2 * (4 * NT * 4), w[2] - w[1]);
       stf4(vo + 3 * (4 * NT * 4), w[1] - w[3]);
     }
-    STAMP(2)          // input transform
     __syncthreads();  // V published
-    STAMP(3)          // barrier 2
 
     // ---- 3. matrix phase: M_pos[tile][cout] += V_pos[tile][k] * U_pos[k][cout], 16 positions
-#ifdef DMH_STAMPS
-    if (!(p.ablate & 2))
-#endif
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const float4 a = ld4(va + q * (4 * NT * 4));
@@ -256,7 +227,6 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
       }
       __builtin_amdgcn_sched_barrier(0);  // keep the refill load here, not next to its consumer
     }
-    STAMP(4)  // matrix phase
   }
 
   // ---- output transform Y = A^T M A, register-local: lane holds M_pos[tile = wm*16 + kq*4 + r][cout = .. + j16]
@@ -288,19 +258,7 @@ __global__ __launch_bounds__(256 * G, 2) void conv_wino_kernel(ConvArgs p) {
   __syncthreads();
   EpilogueRows er(p, b, n0);
   er.template store_rows<TW>(p, slab + (wave & 3) * (32 * EP), (wave & 3) * 32, oy0, ox0);
-#ifdef DMH_STAMPS
-  STAMP(5)  // output transform + row epilogue
-  if (p.stats && lane == 0 && nt == 0 && G == 1) {
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(
-                                p.stats + ((size_t)(b * p.tilesX * p.tilesY + tile_in_sample) * p.Cout) * 2) + wave * 8;
-    for (int i = 0; i < 6; ++i) d[i] = tk[i];
-    d[6] = t_now - t_begin;
-    d[7] = ((unsigned long long)__builtin_amdgcn_s_getreg((6) | (0 << 6) | (31 << 11)) << 32) |
-           __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));  // HW_REG_LDS_ALLOC : HW_REG_HW_ID
-  }
-#else
   er.write_stats(p, lds, tile_in_sample);
-#endif
 }
 
 // transformed weights U = G g G^T in fragment-major order [nt][chunk][pos][nb4][lane][4]:
@@ -363,30 +321,16 @@ int dmh_wino_pack(const float* w, float* wpack, int Cout, int C0, int C1, hipStr
 
 int dmh_wino_launch(const DmhConv* d, int Hout, int Wout, hipStream_t st) {
   ConvArgs a = fill_conv_args(d, Hout, Wout, KC, TH, TW);
-#ifdef DMH_STAMPS
-  {
-    const char* e = getenv("DMH_WINO_ABLATE");
-    a.ablate = e ? atoi(e) : 0;
-  }
-#endif
-  static int wide = -1;  // development knob: DMH_WINO_WIDE=0 disables the 128-channel workgroups
-  if (wide < 0) {
-    const char* e = getenv("DMH_WINO_WIDE");
-    wide = e ? atoi(e) : 1;
-  }
-  if (wide && a.Cout % 128 == 0) {
+  if (a.Cout % 128 == 0) {
     constexpr int LDSW = (2 * SLAB_FLOATS > LDS_FLOATS ? 2 * SLAB_FLOATS : LDS_FLOATS) * 4;  // 69.6 KB
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)conv_wino_kernel<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSW);
-      (void)hipFuncSetAttribute((const void*)conv_wino_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSW);
-      attr = true;
-    }
     dim3 grid(a.tilesX * a.tilesY * a.B, a.Cout / 128);
-    if (d->upsample2)
+    if (d->upsample2) {
+      DMH_RAISE_LDS_ONCE((conv_wino_kernel<1, 2>), LDSW, "dmh_conv2d(winograd)");
       hipLaunchKernelGGL((conv_wino_kernel<1, 2>), grid, dim3(512), LDSW, st, a);
-    else
+    } else {
+      DMH_RAISE_LDS_ONCE((conv_wino_kernel<0, 2>), LDSW, "dmh_conv2d(winograd)");
       hipLaunchKernelGGL((conv_wino_kernel<0, 2>), grid, dim3(512), LDSW, st, a);
+    }
     DMH_CHECK_LAUNCH("dmh_conv2d(winograd, 128-channel workgroups)");
     return DMH_OK;
   }

@@ -18,7 +18,6 @@
 //          scale, two pieces) of the 16x16x32 MFMAs that contract over the pixels — no lane movement between the GEMMs;
 //   pass 2 multiplies channels x pixels (q^T): its accumulators (lane = pixel, registers = d), softmaxed and split, are
 //          the B operand of out^T = ctx^T q^T, whose A operand (the head's context) is split once per workgroup.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -311,10 +310,8 @@ struct RingStager {
 // ------------------------------------------------------------------------------------------ pass 1
 // grid = B * nsplit workgroups; workgroup (b, sp) covers `tiles` sub-tiles of 64 pixels; wave = head.
 // wkv: [head 4][chunk][nb 4: k lo, k hi, v lo, v hi][plane 2][lane 64] x 16 B, then 256 floats 2^-k per (head, nb, col)
-// RES: number of channel chunks whose weight fragments stay in registers for the whole workgroup (2 when C == 64: the
-// 128x128 level, where a workgroup walks 4 sub-tiles and round 1 re-fetched the head's 16 KB of fragments from L2 for each
-// of them); 0: the fragments of a chunk are fetched while the chunk is staged.
-template <int RES>
+// The weight fragments of a chunk are fetched while the chunk is staged (C == 64 runs linattn_kv_ring_kernel instead, which
+// keeps both chunks' fragments in registers).
 __global__ __launch_bounds__(256, 2) void linattn_kv_kernel(const float* __restrict__ x, const float* __restrict__ stats,
                                                             const float* __restrict__ g, const uint4* __restrict__ wkv,
                                                             const float* __restrict__ oscale, float* __restrict__ partial,
@@ -361,13 +358,6 @@ __global__ __launch_bounds__(256, 2) void linattn_kv_kernel(const float* __restr
     st.begin_tile(stats_b, sp * tiles * TP);
     st.issue(0);
   }
-  uint4 wres[RES ? RES : 1][8];
-  if (RES) {
-#pragma unroll
-    for (int ch = 0; ch < RES; ++ch)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) wres[ch][i] = wb[(size_t)(ch * 8 + i) * 64];
-  }
   for (int tI = 0; tI < tiles; ++tI) {
     const int p0 = (sp * tiles + tI) * TP;
     if (p0 >= n) break;
@@ -398,16 +388,11 @@ __global__ __launch_bounds__(256, 2) void linattn_kv_kernel(const float* __restr
       }
 #undef LA_TERM
     };
-    if (RES) {
+    for (int ch = 0; ch < nch; ++ch) {
+      uint4 bq[8];  // this chunk's weight fragments travel while the chunk is staged
 #pragma unroll
-      for (int ch = 0; ch < RES; ++ch) chunk(ch, wres[ch]);
-    } else {
-      for (int ch = 0; ch < nch; ++ch) {
-        uint4 bq[8];  // this chunk's weight fragments travel while the chunk is staged
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bq[i] = wb[(size_t)(ch * 8 + i) * 64];
-        chunk(ch, bq);
-      }
+      for (int i = 0; i < 8; ++i) bq[i] = wb[(size_t)(ch * 8 + i) * 64];
+      chunk(ch, bq);
     }
     const float inv_s = st.inv_scale();
     if (tI + 1 < tiles && p0 + TP < n) {  // the next sub-tile's first chunk travels during the softmax / context math
@@ -821,16 +806,8 @@ struct FuseOut {
 constexpr int YP = 68;                                  // pitch (floats) of a pixel's 64 channels in the exchange buffer
 constexpr int YX_BYTES = 4 * TP * YP * 4;               // [head][pixel][channel] partial sums: 69632 B
 
-// DMH_HX_SLOT (never the product: `make hx`, tools/experiments/hazard_hunt/) rebuilds round 2's open case: a four-float LDS
-// slot holding 1.0, written once at kernel start, read after the exchange barrier of every sub-tile and multiplied into the
-// per-thread to_out scales — a change that cannot alter a result and did, for a few pixels of some launches under load.
-#if defined(DMH_HX_SLOT) && defined(DMH_HX_LB1)
-#define DMH_QO_WAVES 1
-#else
-#define DMH_QO_WAVES 2
-#endif
 template <bool FUSE>
-__global__ __launch_bounds__(256, DMH_QO_WAVES) void linattn_qo_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+__global__ __launch_bounds__(256, 2) void linattn_qo_kernel(const float* __restrict__ x, const float* __restrict__ stats,
                                                             const float* __restrict__ g, const uint4* __restrict__ wq,
                                                             const float* __restrict__ oscale, const float* __restrict__ ctxm,
                                                             float* __restrict__ out, int n, int C, int nblk, int tiles,
@@ -839,10 +816,6 @@ __global__ __launch_bounds__(256, DMH_QO_WAVES) void linattn_qo_kernel(const flo
   constexpr int NBUF = FUSE ? 1 : 2;
   unsigned char* tiles_lds = smem;
   float* yx = reinterpret_cast<float*>(smem + TILE_BYTES);  // FUSE only
-#ifdef DMH_HX_SLOT
-  float* hx_slot = reinterpret_cast<float*>(smem + TILE_BYTES + YX_BYTES);
-  if (FUSE && threadIdx.x == 0) st4(hx_slot, make_float4(1.f, 1.f, 1.f, 1.f));   // (the first staging barrier publishes it)
-#endif
 
   const int jb = blockIdx.x / nblk, blk = blockIdx.x % nblk;
   if (rows && jb >= rows[0]) return;   // (a row subset, common.h)
@@ -1127,17 +1100,6 @@ __global__ __launch_bounds__(256, DMH_QO_WAVES) void linattn_qo_kernel(const flo
       oq.w *= inv_o;
       __syncthreads();
       LSTAMP(3)  // exchange write + barrier
-#ifdef DMH_HX_SLOT
-#ifdef DMH_HX_CONST
-      const float4 hx = make_float4(1.f, 1.f, 1.f, 1.f);
-#else
-      const float4 hx = ld4(hx_slot);
-#endif
-      const float4 oqx = make_float4(oq.x * hx.x, oq.y * hx.y, oq.z * hx.z, oq.w * hx.w);
-#define DMH_OQ oqx
-#else
-#define DMH_OQ oq
-#endif
       // 64 pixels x 16 channel quads: sum the heads, undo the weight scale, + bias, LayerNorm over the 64 channels (two
       // passes, as chan_layernorm_kernel), * g, + x
 #pragma unroll
@@ -1147,10 +1109,10 @@ __global__ __launch_bounds__(256, DMH_QO_WAVES) void linattn_qo_kernel(const flo
         const float* yp = yx + pl * YP + quad * 4;
         const float4 y0 = ld4(yp), y1 = ld4(yp + TP * YP), y2 = ld4(yp + 2 * TP * YP), y3 = ld4(yp + 3 * TP * YP);
         float4 v;
-        v.x = fmaf((y0.x + y1.x) + (y2.x + y3.x), DMH_OQ.x, bq4.x);
-        v.y = fmaf((y0.y + y1.y) + (y2.y + y3.y), DMH_OQ.y, bq4.y);
-        v.z = fmaf((y0.z + y1.z) + (y2.z + y3.z), DMH_OQ.z, bq4.z);
-        v.w = fmaf((y0.w + y1.w) + (y2.w + y3.w), DMH_OQ.w, bq4.w);
+        v.x = fmaf((y0.x + y1.x) + (y2.x + y3.x), oq.x, bq4.x);
+        v.y = fmaf((y0.y + y1.y) + (y2.y + y3.y), oq.y, bq4.y);
+        v.z = fmaf((y0.z + y1.z) + (y2.z + y3.z), oq.z, bq4.z);
+        v.w = fmaf((y0.w + y1.w) + (y2.w + y3.w), oq.w, bq4.w);
         float sm = (v.x + v.y) + (v.z + v.w);
         sm = row16_sum(sm);
         const float mean = sm / 64.f;
@@ -1293,25 +1255,13 @@ extern "C" int dmh_linattn_fused_context(const float* x, const float* stats, con
   const int tiles = fused_tiles(B, n), nsplit = cdiv(cdiv(n, TP), tiles);
   const uint4* wkv = reinterpret_cast<const uint4*>(wpack + (int64_t)C * 128);
   const float* osc_kv = wpack + (int64_t)C * 384 + 128;
-  static const int use_ring = [] {   // development knob for same-box A/Bs: DMH_LA_RING=0 -> round 2's register staging
-    const char* e = getenv("DMH_LA_RING");
-    return e ? atoi(e) : 1;
-  }();
-  if (C == 2 * KC && use_ring) {
+  if (C == 2 * KC) {   // the 64-channel levels: the raw ring (LDS-DMA staging)
     constexpr int LDS = 4 * TILE_BYTES + RingStager::BYTES;
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)linattn_kv_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      DMH_REQUIRE(e == hipSuccess, "dmh_linattn_fused_context: cannot raise the LDS limit");
-      attr = true;
-    }
+    DMH_RAISE_LDS_ONCE(linattn_kv_ring_kernel, LDS, "dmh_linattn_fused_context");
     hipLaunchKernelGGL(linattn_kv_ring_kernel, dim3(B * nsplit), dim3(256), LDS, (hipStream_t)stream, x, stats, ln_g, wkv,
                        osc_kv, partial, n, C, nsplit, tiles, rows);
-  } else if (C == 2 * KC)
-    hipLaunchKernelGGL(linattn_kv_kernel<2>, dim3(B * nsplit), dim3(256), 2 * TILE_BYTES, (hipStream_t)stream, x, stats, ln_g,
-                       wkv, osc_kv, partial, n, C, nsplit, tiles, rows);
-  else
-    hipLaunchKernelGGL(linattn_kv_kernel<0>, dim3(B * nsplit), dim3(256), 2 * TILE_BYTES, (hipStream_t)stream, x, stats, ln_g,
+  } else
+    hipLaunchKernelGGL(linattn_kv_kernel, dim3(B * nsplit), dim3(256), 2 * TILE_BYTES, (hipStream_t)stream, x, stats, ln_g,
                        wkv, osc_kv, partial, n, C, nsplit, tiles, rows);
   DMH_CHECK_LAUNCH("dmh_linattn_fused_context");
   return DMH_OK;
@@ -1400,17 +1350,8 @@ extern "C" int dmh_linattn_fused_apply_out(const float* x, const float* stats, c
   fo.g_out = out_ln_g;
   fo.y = y;
   fo.eps = eps;
-#ifdef DMH_HX_SLOT
-  constexpr int LDS = TILE_BYTES + YX_BYTES + 16;
-#else
   constexpr int LDS = TILE_BYTES + YX_BYTES;
-#endif
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)linattn_qo_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    DMH_REQUIRE(e == hipSuccess, "dmh_linattn_fused_apply_out: cannot raise the LDS limit");
-    attr = true;
-  }
+  DMH_RAISE_LDS_ONCE(linattn_qo_kernel<true>, LDS, "dmh_linattn_fused_apply_out");
   hipLaunchKernelGGL(linattn_qo_kernel<true>, dim3(B * nblk), dim3(256), LDS, (hipStream_t)stream, x, stats, ln_g, wq,
                      osc_q, ctx, nullptr, n, C, nblk, tiles, scale, fo, rows);
   DMH_CHECK_LAUNCH("dmh_linattn_fused_apply_out");

@@ -16,16 +16,13 @@ trunk's modules, their order and the skip stack come from ``layout.unet_layout``
   torch.cat    never materialises: convs take two source pointers
   Upsample     nearest x2 is index math inside the 3x3 gather
 """
-import os
-
 import torch
 
 from . import ops
 from .layout import ATTN_SCALE, HIDDEN, sinusoidal_freq, unet_layout
 
-# development knob: '0' = final_conv as its own launch over the stored output of the last ResnetBlock
-FUSED_FINAL = os.environ.get('DMH_FUSED_FINAL', '1') != '0'
-FUSED_LINATTN = os.environ.get('DMH_FUSED_LINATTN', '1') != '0'   # development knob: '0' = separate LayerNorm / to_qkv / core
+# False = final_conv as its own launch over the stored output of the last ResnetBlock (a parity test compares the two)
+FUSED_FINAL = True
 
 
 class _Res:
@@ -108,7 +105,7 @@ class UnetEngine:
             a.linear = n.kind == 'linattn'
             a.ln_g = f32(k['g']).reshape(-1).contiguous()
             a.pla = None
-            if a.linear and c % 32 == 0 and FUSED_LINATTN:
+            if a.linear and c % 32 == 0:
                 # LayerNorm + to_qkv + both attention passes in two kernels (ops.linear_attention_fused)
                 a.qkv = None
                 a.pla = ops.PackedLinAttn(f32(k['qkv']))
@@ -154,17 +151,13 @@ class UnetEngine:
         rows = self._rows
         y1, st1 = pre if pre is not None else ops.conv2d(r.conv1, x0, x1, want_stats=True, rows=rows)
         ss = ss_all[:, r.ss_off:r.ss_off + 2 * r.cout]
-        if ops.STATIC_BOUND:
-            coef1, bound1 = ops.gn_finalize(st1, r.g1, r.b1, hw, self.groups, ss, want_bound=True, rows=rows)
-        else:
-            coef1, bound1 = ops.gn_finalize(st1, r.g1, r.b1, hw, self.groups, ss, rows=rows), None
+        coef1, bound1 = ops.gn_finalize(st1, r.g1, r.b1, hw, self.groups, ss, want_bound=True, rows=rows)
         y2, st2 = ops.conv2d(r.conv2, y1, in_coef=coef1, want_stats=True, in_bound=bound1, rows=rows)
         coef2 = ops.gn_finalize(st2, r.g2, r.b2, hw, self.groups, rows=rows)
         if final is not None:
             return ops.conv2d(r.res, x0, x1, res=y2, res_coef=coef2, final=final, keep_out=keep_out, fin_out=fin_out, rows=rows)
         if r.res is not None:
-            if pixel_stats and r.cout == 64 and r.res.k == 1 and 64 in ops.PIXEL_STATS_FUSABLE and ops.f16x3_default() \
-                    and os.environ.get('DMH_CONV_PIXEL_STATS', '1') != '0':      # (knob: same-box A/Bs)
+            if pixel_stats and r.cout == 64 and r.res.k == 1 and ops.f16x3_default():
                 # (the up path at dim 64: the LayerNorm statistics of the LinearAttention behind this block come out of the
                 #  res_conv launch that finishes it — DmhConv.pix_stats — instead of a dmh_pixel_stats pass over its output)
                 return ops.conv2d(r.res, x0, x1, res=y2, res_coef=coef2, pixel_stats=True, rows=rows)

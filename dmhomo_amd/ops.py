@@ -14,8 +14,6 @@ from . import _lib
 from ._lib import call, ptr, lib
 
 F32 = torch.float32
-# DMH_UP_SUBPIXEL=0: keep Upsample + conv3x3 as one 3x3 conv over the (virtually) upsampled input
-SUBPIXEL_UP = __import__('os').environ.get('DMH_UP_SUBPIXEL', '1') != '0'
 
 
 def _empty(shape, like, dtype=F32):
@@ -78,7 +76,7 @@ class PackedConv:
         cout, cin, kh, kw = w.shape
         assert cin == c0 + c1 and kh == kw, (w.shape, c0, c1)
         self._w = w
-        n_up2 = lib().dmh_conv_up2_pack_floats(cout, c0) if (upsample2 and kh == 3 and c1 == 0 and subpixel and SUBPIXEL_UP) else -1
+        n_up2 = lib().dmh_conv_up2_pack_floats(cout, c0) if (upsample2 and kh == 3 and c1 == 0 and subpixel) else -1
         self._up2 = n_up2 > 0
         if self._up2:                     # Upsample + conv3x3 as four 2x2 sub-pixel convs (upsample2 = 2)
             self.wpack = _empty((n_up2,), w)
@@ -189,11 +187,6 @@ def conv2d(pc, src0, src1=None, in_coef=None, res=None, res_coef=None, want_stat
 
 
 # ------------------------------------------------------------------ normalisation glue
-# development knob (A/B runs): DMH_CONV_STATIC_BOUND=0 lets the fp16-piece convs search their staged tiles for the block
-# maximum even where the producer's GroupNorm statistics bound it
-STATIC_BOUND = os.environ.get('DMH_CONV_STATIC_BOUND', '1') != '0'
-
-
 def gn_finalize(stats, gamma, beta, hw, groups, ss=None, eps=1e-5, want_bound=False, rows=None):
     """N2: stats (B,tiles,C,2) -> coef (B,2,C).  ss: (B, >=2C) view whose row b starts with (scale[C], shift[C]).
     want_bound: -> (coef, bound) with bound (B, groups) >= |a*x + b| over each (sample, group): ``conv2d(in_bound=)``."""
@@ -214,8 +207,7 @@ def gn_finalize(stats, gamma, beta, hw, groups, ss=None, eps=1e-5, want_bound=Fa
 
 
 # widths whose ResnetBlock epilogue can hand the LayerNorm statistics to the LinearAttention behind it
-# (development knob DMH_FUSED_PIXEL_STATS=0: the standalone dmh_pixel_stats pass everywhere, for A/B runs)
-PIXEL_STATS_FUSABLE = () if os.environ.get('DMH_FUSED_PIXEL_STATS') == '0' else (64, 128, 256)
+PIXEL_STATS_FUSABLE = (64, 128, 256)
 
 
 def gn_silu_residual(y, coef, res, pixel_stats=False, eps=1e-5, rows=None):

@@ -109,7 +109,7 @@ int dmh_rows_from_keep(const uint8_t* keep, int B, int extra, int32_t* rows, voi
  * K1/K2  convolution as an implicit GEMM.  fp32 tensors in and out; by default the products run on the fp16
  * matrix cores with every fp32 operand carried as block-scaled fp16 pieces (three v_mfma_f32_16x16x32_f16 per
  * product block, fp32 accumulation; error at the level of the fp32 accumulation rounding, fp32 exponent range —
- * DESIGN.md 3.1).  DMH_CONV3_VARIANT=0..3 / 6 (environment, read once) selects the exact-fp32 MFMA kernels.
+ * DESIGN.md 3.1).  DMH_CONV3_VARIANT=0 / 6 (environment, read once) selects the exact-fp32 MFMA kernels.
  * ------------------------------------------------------------------------------------- */
 typedef struct DmhConv {
   uint64_t struct_size; /* sizeof(DmhConv) of the header the caller was built against: dmh_conv2d refuses any other value
@@ -395,7 +395,7 @@ int dmh_dlt_homography(const float* flow, double* ws, double* Hout, int B, int H
  *   KH = 2      : 'valid' 2x2 conv (p = 0) over a stored input [B][H+1][W+1][C0] — the space-to-depth form
  *                 (dmh_s2d_shift) of the 4x4 / stride-2 Downsample conv (CFG:110-111).
  * KH = 2, 3: fp16 pieces of both operands on the fp16 matrix cores, fp32 accumulate (error at the fp32-accumulation
- * level; DMH_WGRAD_VARIANT=0: exact fp32 everywhere); KH = 1, 7: exact fp32 (v_mfma_f32_16x16x4_f32).  Deterministic
+ * level); KH = 1, 7: exact fp32 (v_mfma_f32_16x16x4_f32).  Deterministic
  * (pixel splits reduced in a fixed order).  The DATA gradient is
  * dmh_conv2d itself on dy with the weight flipped in both taps and transposed in (Cout, Cin).
  * dy: NHWC [B][H][W][Cout]; dw: OIHW [Cout][C0+C1][KH][KH]; db: [Cout] or NULL; work: ..._workspace_floats floats. */

@@ -334,3 +334,44 @@ def test_bench_plain_run_leaves_every_other_leg_to_full():
     assert a.full and not any(getattr(a, k) for k in legs) and (a.steps, a.warmup) == (5, 2)
     a = bench.parse_args(['--full', '--no-roofline', '--no-cpu-baseline'])
     assert a.no_roofline and a.no_cpu_baseline and not (a.no_traffic or a.no_variants or a.no_phases)
+
+
+def test_runtime_switches_are_the_documented_ones():
+    """the environment variables the library (every getenv in dmhomo_amd/csrc) and the package (every 'DMH_*' string in
+    dmhomo_amd/**/*.py: each one is the name of an os.environ read) look at are exactly the rows of DESIGN.md's "Run-time
+    switches" table — a development knob that comes back has to be documented there or fails here.  DMH_WINO_ABLATE, the
+    diagnostic build's ablation word, is the one extra name, and may only stand inside ``#ifdef DMH_STAMPS``."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    design = open(os.path.join(root, 'DESIGN.md')).read()
+    section = design.split('Run-time switches\n', 1)[1].split('\n## ', 1)[0]
+    documented = set(re.findall(r'^\| `(DMH_[A-Z0-9_]+)` \|', section, flags=re.M))
+    assert len(documented) == 6 and 'DMH_CONV3_VARIANT' in documented, documented
+
+    found, stamps_only = set(), 'DMH_WINO_ABLATE'
+    sources = sorted(glob.glob(os.path.join(root, 'dmhomo_amd', 'csrc', '*')))
+    assert any(s.endswith('conv_f16x3.hip') for s in sources)
+    for path in sources:
+        if not os.path.isfile(path) or not path.endswith(('.hip', '.h', '.cpp', '.hpp')):
+            continue
+        guards = []                                  # the #if stack: True where the branch is `#ifdef DMH_STAMPS` itself
+        for line in open(path):
+            s = line.strip()
+            if s.startswith('#if'):
+                guards.append(re.fullmatch(r'#ifdef\s+DMH_STAMPS', s) is not None)
+            elif s.startswith('#else') or s.startswith('#elif'):
+                guards[-1] = False
+            elif s.startswith('#endif'):
+                guards.pop()
+            for name in re.findall(r'getenv\s*\(\s*"([^"]*)"', line):
+                found.add(name)
+                assert name != stamps_only or any(guards), f'{path}: {stamps_only} is read outside #ifdef DMH_STAMPS'
+            assert 'getenv' not in line or re.search(r'getenv\s*\(\s*"', line), f'{path}: getenv of a computed name: {s}'
+        assert not guards, path
+    py = sorted(glob.glob(os.path.join(root, 'dmhomo_amd', '**', '*.py'), recursive=True))
+    assert len(py) >= 10
+    for path in py:
+        found |= set(re.findall(r'''['"](DMH_[A-Z0-9_]+)['"]''', open(path).read()))
+    assert stamps_only in found
+    assert found - {stamps_only} == documented, (sorted(found - documented), sorted(documented - found))
