@@ -161,6 +161,10 @@ SIGNATURES = {
     'dmh_flow_warp': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               C.c_void_p]),
     'dmh_dlt_homography': (c_int, [c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_post_process': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_preview_sheet': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  C.c_void_p]),
+    'dmh_homography_warp': (c_int, [c_f32p, C.c_void_p, c_f32p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
 }
 
 DLT_BLOCKS = 64

@@ -1,36 +1,9 @@
 // K7-K9 — condition builder & geometry: homography -> flow -> HSV image, bilinear flow warp,
 // flow -> homography (DLT normal equations).  Mirrors the reference's op order exactly where
 // integers come out (grid-sample corner indices): no FMA contraction in this file.
-#include "common.h"
+#include "geometry_dev.h"   // flow_pixel_to_rgb (G3), flow_warp_taps / flow_warp_sample (G4): shared with preview.hip
 
 #pragma clang fp contract(off)
-
-// G3: flow_to_image DDP:1479-1485 + matplotlib.colors.hsv_to_rgb for one pixel
-__device__ __forceinline__ void flow_pixel_to_rgb(float u, float v, float max_flow, float& r, float& g, float& bl) {
-  const float n = 8.f;
-  const float mag = sqrtf(u * u + v * v);
-  const float ang = atan2f(v, u);
-  float hh = fmodf(ang / 6.283185307179586f + 1.f, 1.f);  // np.mod(angle / (2 pi) + 1, 1), operand >= 0.5
-  float ss = fminf(fmaxf(mag * n / max_flow, 0.f), 1.f);
-  float vv = fminf(fmaxf(n - ss, 0.f), 1.f);
-  // matplotlib.colors.hsv_to_rgb: i = (h*6).astype(int); f = h*6 - i is float64 there (f32 - int64),
-  // so q and t are formed in f64 and rounded to fp32 on store; p stays fp32.
-  const float h6 = hh * 6.0f;
-  const int i = (int)h6;
-  const double f = (double)h6 - (double)i;
-  const float pp = vv * (1.0f - ss);
-  const float qq = (float)((double)vv * (1.0 - (double)ss * f));
-  const float tt = (float)((double)vv * (1.0 - (double)ss * (1.0 - f)));
-  switch (i % 6) {
-    case 0: r = vv; g = tt; bl = pp; break;
-    case 1: r = qq; g = vv; bl = pp; break;
-    case 2: r = pp; g = vv; bl = tt; break;
-    case 3: r = pp; g = qq; bl = vv; break;
-    case 4: r = tt; g = pp; bl = vv; break;
-    default: r = vv; g = pp; bl = qq; break;
-  }
-  if (ss == 0.f) r = g = bl = vv;
-}
 
 // ---------------------------------------------------------------------------------------------
 // G2 + G3.  get_flow_np DDP:954-967 in float64 on an integer grid, cast to fp32; then
@@ -164,34 +137,10 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict_
   if (p >= H * W) return;
   const int yi = p / W, xi = p % W;
   const size_t hw = (size_t)H * W;
-  const float vx = (float)xi + flow[((size_t)b * 2 + 0) * hw + p];
-  const float vy = (float)yi + flow[((size_t)b * 2 + 1) * hw + p];
-  const float gx = 2.0f * vx / (float)(W - 1) - 1.0f;
-  const float gy = 2.0f * vy / (float)(H - 1) - 1.0f;
-  float ix = (gx + 1.f) * ((float)(W - 1) / 2.f);
-  float iy = (gy + 1.f) * ((float)(H - 1) / 2.f);
-  ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
-  iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const int x0 = (int)fx0, y0 = (int)fy0;
-  if (x0o) x0o[(size_t)b * hw + p] = x0;
-  if (y0o) y0o[(size_t)b * hw + p] = y0;
-  const float w = ix - fx0, e = (fx0 + 1.f) - ix, n = iy - fy0, s = (fy0 + 1.f) - iy;
-  const float wnw = s * e, wne = s * w, wsw = n * e, wse = n * w;
-  const bool x1ok = x0 + 1 <= W - 1, y1ok = y0 + 1 <= H - 1;
-  const int x1 = x1ok ? x0 + 1 : x0, y1 = y1ok ? y0 + 1 : y0;
-  for (int c = 0; c < C; ++c) {
-    const float* xc = x + ((size_t)b * C + c) * hw;
-    const float nw = xc[(size_t)y0 * W + x0];
-    const float ne = x1ok ? xc[(size_t)y0 * W + x1] : 0.f;
-    const float sw = y1ok ? xc[(size_t)y1 * W + x0] : 0.f;
-    const float se = (x1ok && y1ok) ? xc[(size_t)y1 * W + x1] : 0.f;
-    float acc = nw * wnw;
-    acc = fmaf(ne, wne, acc);
-    acc = fmaf(sw, wsw, acc);
-    acc = fmaf(se, wse, acc);
-    out[((size_t)b * C + c) * hw + p] = acc;
-  }
+  const FlowWarpTaps t = flow_warp_taps(flow[((size_t)b * 2 + 0) * hw + p], flow[((size_t)b * 2 + 1) * hw + p], xi, yi, H, W);
+  if (x0o) x0o[(size_t)b * hw + p] = t.x0;
+  if (y0o) y0o[(size_t)b * hw + p] = t.y0;
+  for (int c = 0; c < C; ++c) out[((size_t)b * C + c) * hw + p] = flow_warp_sample(x + ((size_t)b * C + c) * hw, t, W);
 }
 
 // ---------------------------------------------------------------------------------------------

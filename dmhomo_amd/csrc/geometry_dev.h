@@ -1,0 +1,83 @@
+// Per-pixel device functions of the geometry kernels, shared by geometry.hip (G3 flow_to_image, G4 flow_warp) and preview.hip
+// (the preview sheets fuse both): one definition, so the fused panels are bit for bit what the stand-alone kernels write.
+// They mirror the reference's op order where integers come out (grid-sample corner indices): no FMA contraction here.
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+// G3: flow_to_image DDP:1479-1485 + matplotlib.colors.hsv_to_rgb for one pixel
+__device__ __forceinline__ void flow_pixel_to_rgb(float u, float v, float max_flow, float& r, float& g, float& bl) {
+  const float n = 8.f;
+  const float mag = sqrtf(u * u + v * v);
+  const float ang = atan2f(v, u);
+  float hh = fmodf(ang / 6.283185307179586f + 1.f, 1.f);  // np.mod(angle / (2 pi) + 1, 1), operand >= 0.5
+  float ss = fminf(fmaxf(mag * n / max_flow, 0.f), 1.f);
+  float vv = fminf(fmaxf(n - ss, 0.f), 1.f);
+  // matplotlib.colors.hsv_to_rgb: i = (h*6).astype(int); f = h*6 - i is float64 there (f32 - int64),
+  // so q and t are formed in f64 and rounded to fp32 on store; p stays fp32.
+  const float h6 = hh * 6.0f;
+  const int i = (int)h6;
+  const double f = (double)h6 - (double)i;
+  const float pp = vv * (1.0f - ss);
+  const float qq = (float)((double)vv * (1.0 - (double)ss * f));
+  const float tt = (float)((double)vv * (1.0 - (double)ss * (1.0 - f)));
+  switch (i % 6) {
+    case 0: r = vv; g = tt; bl = pp; break;
+    case 1: r = qq; g = vv; bl = pp; break;
+    case 2: r = pp; g = vv; bl = tt; break;
+    case 3: r = pp; g = qq; bl = vv; break;
+    case 4: r = tt; g = pp; bl = vv; break;
+    default: r = vv; g = pp; bl = qq; break;
+  }
+  if (ss == 0.f) r = g = bl = vv;
+}
+
+// G4.  flow_warp = grid_sample(bilinear, border, align_corners=True) of torch's CPU kernel, for the pixel (xi, yi) moved by
+// (fu, fv):
+//   g  = 2.0*v/(W-1) - 1.0;  ix = (g+1)*((W-1)/2);  ix = min(W-1, max(ix, 0));  x0 = floor(ix)
+//   w = ix-x0, e = (x0+1)-ix, n = iy-y0, s = (y0+1)-iy
+//   out = fma(se, n*w, fma(sw, n*e, fma(ne, s*w, nw*(s*e))))
+// The corner indices always lie inside the image (the coordinate is clipped); a corner one past the last row / column is
+// read as 0 (its weight is 0 there).
+struct FlowWarpTaps {
+  int x0, y0, x1, y1;
+  bool x1ok, y1ok;
+  float wnw, wne, wsw, wse;
+};
+__device__ __forceinline__ FlowWarpTaps flow_warp_taps(float fu, float fv, int xi, int yi, int H, int W) {
+  FlowWarpTaps t;
+  const float vx = (float)xi + fu;
+  const float vy = (float)yi + fv;
+  const float gx = 2.0f * vx / (float)(W - 1) - 1.0f;
+  const float gy = 2.0f * vy / (float)(H - 1) - 1.0f;
+  float ix = (gx + 1.f) * ((float)(W - 1) / 2.f);
+  float iy = (gy + 1.f) * ((float)(H - 1) / 2.f);
+  ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
+  iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
+  const float fx0 = floorf(ix), fy0 = floorf(iy);
+  t.x0 = (int)fx0;
+  t.y0 = (int)fy0;
+  const float w = ix - fx0, e = (fx0 + 1.f) - ix, n = iy - fy0, s = (fy0 + 1.f) - iy;
+  t.wnw = s * e;
+  t.wne = s * w;
+  t.wsw = n * e;
+  t.wse = n * w;
+  t.x1ok = t.x0 + 1 <= W - 1;
+  t.y1ok = t.y0 + 1 <= H - 1;
+  t.x1 = t.x1ok ? t.x0 + 1 : t.x0;
+  t.y1 = t.y1ok ? t.y0 + 1 : t.y0;
+  return t;
+}
+// one channel plane xc [H][W] sampled at the taps
+__device__ __forceinline__ float flow_warp_sample(const float* __restrict__ xc, const FlowWarpTaps& t, int W) {
+  const float nw = xc[(size_t)t.y0 * W + t.x0];
+  const float ne = t.x1ok ? xc[(size_t)t.y0 * W + t.x1] : 0.f;
+  const float sw = t.y1ok ? xc[(size_t)t.y1 * W + t.x0] : 0.f;
+  const float se = (t.x1ok && t.y1ok) ? xc[(size_t)t.y1 * W + t.x1] : 0.f;
+  float acc = nw * t.wnw;
+  acc = fmaf(ne, t.wne, acc);
+  acc = fmaf(sw, t.wsw, acc);
+  acc = fmaf(se, t.wse, acc);
+  return acc;
+}

@@ -6,6 +6,7 @@ Host-side mirror of ``DGM/denoising_diffusion_models/denoising_diffusion_pytorch
 helpers DDP:913-988,1262-1299,1471-1486,1558-1678 and the ``Trainer`` surface DDP:1681-2021.
 All tensor values come from libdmhomo_hip.so; there is no CPU path.
 """
+import math
 import os
 from pathlib import Path
 
@@ -16,6 +17,8 @@ from torch import nn
 from . import _params as P
 from . import ops
 from .engine import UnetEngine
+from .preview import (visulize_flow, postProcess, postProcess_cv2, make_gif, save_image, save_preview_sheets,  # noqa: F401
+                      square_rows, num_to_groups)
 from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
 from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
 
@@ -601,7 +604,12 @@ class SyntheticConditions:
 class Trainer(object):
     """DDP:1681-2021.  Keeps the constructor, ``save`` / ``load`` (checkpoint dict layout of DDP:1786-1802)
     and ``sample(idx, rank, step)``.  ``folder`` may be an iterator of (12-channel batch, classes) instead of the
-    reference's dataset directory (the CA-Homo dataset path is outside the hot path); ``train`` is a §8f row."""
+    reference's dataset directory (the CA-Homo dataset path is outside the hot path); ``train`` is a §8f row.
+
+    ``preview`` (class attribute, off by default): write the reference's sample sheets — ``train`` at every
+    ``save_and_sample_every``-th step (DDP:1871-1935), ``sample`` at every 100th ``step`` (DDP:1972-2019)."""
+
+    preview = False
 
     def __init__(self, diffusion_model, folder, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_horizontal_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10,
@@ -681,9 +689,9 @@ class Trainer(object):
 
     def train(self, log=None):
         """DDP:1828-1940: gradient accumulation, clip_grad_norm_(1.0), Adam, EMA, checkpoints (the latest as 9999 every
-        500 steps, numbered ones every ``save_and_sample_every``).  The PNG/GIF sample dumps of DDP:1871-1935 are
-        visualisation and stay out.  Ranks > 0 of a torch.distributed run train in lock-step (gradients averaged by
-        one RCCL all-reduce per step) and leave EMA / checkpoints to rank 0, like accelerate's main process."""
+        500 steps, numbered ones every ``save_and_sample_every``).  The PNG/GIF sample dumps of DDP:1871-1935 are written
+        with ``preview`` set (``_preview_milestone``).  Ranks > 0 of a torch.distributed run train in lock-step (gradients
+        averaged by         one RCCL all-reduce per step) and leave EMA / checkpoints to rank 0, like accelerate's main process."""
         import torch.distributed as dist
         ts = self.train_step_engine()
         dev = next(self.model.parameters()).device
@@ -702,17 +710,77 @@ class Trainer(object):
                 if self.step % 500 == 0:
                     self.save(9999)
                 if self.step % self.save_and_sample_every == 0:
-                    self.save(self.step // self.save_and_sample_every)
+                    milestone = self.step // self.save_and_sample_every
+                    if self.preview:
+                        self._preview_milestone(data, milestone, dev)
+                    self.save(milestone)
         if main:
             print('training complete')
 
+    def _preview_milestone(self, data, milestone, dev):
+        """DDP:1871-1934: the conditions of the last training batch repeated to ``num_samples``, sampled from the EMA model in
+        groups of ``batch_size``, written as sample-{m}-source.png / sample-{m}-target.png (BGR, nrow = int(sqrt(num_samples)))
+        and a two-frame GIF.  Differences from the reference, both stated here: the classes are drawn from
+        randint(0, min(5, num_classes)) — the reference draws randint(0, 5) (DDP:1890), which is an invalid id for a model
+        with fewer than 5 classes — and the generators the draws come from (torch's CPU / device generators or the sampler's
+        keyed state) are put back afterwards, so a run with previews trains on the same noise as one without."""
+        ema_model = self.ema.ema_model
+        rng = getattr(ema_model, 'rng', None)
+        cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        snap = rng.snapshot(dev) if isinstance(rng, DeviceRng) else None
+        try:
+            with torch.no_grad():
+                n_all = self.num_samples
+                cond = data[0].to(dev)
+                mask = cond[:, -6:-5].repeat(n_all, 1, 1, 1)[:n_all]
+                rgb_flows = cond[:, -5:-2].repeat(n_all, 1, 1, 1)[:n_all]
+                flows = cond[:, -2:].repeat(n_all, 1, 1, 1)[:n_all]
+                emb = getattr(getattr(ema_model, 'model', None), 'classes_emb', None)
+                num_classes = emb.num_embeddings if emb is not None else 5
+                bufs = [ema_model.sample(classes=torch.randint(0, min(5, int(num_classes)), (n,)).to(dev),
+                                         rgb_flow=rgb_flows[:n].contiguous(), flow=flows[:n].contiguous(),
+                                         mask=mask[:n].contiguous())
+                        for n in num_to_groups(n_all, self.batch_size)]
+                all_images, all_mask, all_flows = (torch.cat([b[i] for b in bufs], dim=0) for i in range(3))
+            self.results_folder.mkdir(exist_ok=True)
+            source = str(self.results_folder / f'sample-{milestone}-source.png')
+            target = str(self.results_folder / f'sample-{milestone}-target.png')
+            save_preview_sheets(all_images, all_mask, all_flows, source, target, nrow=int(math.sqrt(n_all)))
+            make_gif(source, target, milestone)
+        finally:
+            torch.set_rng_state(cpu_state)
+            torch.cuda.set_rng_state(dev_state, dev)
+            if snap is not None:
+                rng.restore(snap, dev)
+
     def sample(self, idx, rank, step=1):
-        """DDP:1941-2021 without the every-100-steps PNG/GIF dumps (visualisation is out of scope)."""
-        data = next(self.dl)
+        """DDP:1941-2021.  With ``preview`` set, every 100th ``step`` also writes the flow-remap and homography-warp sheets and
+        their GIFs under generate_training_pairs/ (DDP:1972-2019); the record returned is the same either way."""
         dev = torch.device('cuda', rank) if isinstance(rank, int) else torch.device(rank)
+        dump = self.preview and step % 100 == 0
+        if dump and self.image_size != 256:
+            raise ValueError(f'Trainer.sample with preview: the homography-warp sheet puts a (256, 256) canvas beside the '
+                             f'record (DDP:1527), so it needs image_size 256, not {self.image_size}')
+        data = next(self.dl)
         rgb_flows = data[0][:, -5:-2].to(dev)
         flows = data[0][:, -2:].to(dev).contiguous()
         mask = data[0][:, -6:-5].to(dev)
         with torch.no_grad():
             all_images = self.ema.ema_model.sample(classes=data[1].to(dev), rgb_flow=rgb_flows, flow=flows, mask=mask)
-        return saveTrainPair(all_images[0], mask=all_images[1], flows=all_images[2])
+        ret = saveTrainPair(all_images[0], mask=all_images[1], flows=all_images[2])
+        if dump:
+            n = square_rows(all_images[0].shape[0])
+            nrow = int(math.sqrt(n))
+            os.makedirs('generate_training_pairs', exist_ok=True)
+            stem = f'idx_{idx}_step_{step}_rank_{rank}'
+            source, target = (f'generate_training_pairs/{stem}_sample-{k}_flowRemap.png' for k in ('source', 'target'))
+            save_preview_sheets(all_images[0][:n], all_images[1][:n], all_images[2][:n], source, target, nrow=nrow)
+            make_gif(source, target, f'{stem}_flowRemap')
+            permute = [2, 1, 0]                                    # from rgb to bgr, DDP:2005
+            img1s, warp_img2s = postProcess_cv2(imgs=ret['imgs'][:n], homos=np.asarray(ret['homos']).reshape(-1, 3, 3)[:n],
+                                                rank=rank)
+            source, target = (f'generate_training_pairs/{stem}_sample-{k}_homoWarp.png' for k in ('source', 'target'))
+            save_image(img1s[:, permute], source, nrow=nrow)
+            save_image(warp_img2s[:, permute], target, nrow=nrow)
+            make_gif(source, target, f'{stem}_homoWarp')
+        return ret

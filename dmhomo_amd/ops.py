@@ -624,6 +624,55 @@ def dlt_homography(flow):
     return out
 
 
+# ------------------------------------------------------------------ sample preview sheets (DDP:1489-1555)
+def _preview_inputs(img, mask, flow):
+    B, C6, H, W = img.shape
+    assert C6 == 6 and mask.shape == (B, 1, H, W) and flow.shape == (B, 2, H, W), (img.shape, mask.shape, flow.shape)
+    return B, H, W
+
+
+def post_process(img, mask, flow):
+    """postProcess DDP:1505-1517 in one launch: img (B,6,H,W), mask (B,1,H,W), flow (B,2,H,W) ->
+    buf1 = [img1 | img1 | mask x3 | flow_vis], buf2 = [img2 | flow_warp(img2, flow) | mask x3 | flow_vis], (B,3,H,4W)."""
+    B, H, W = _preview_inputs(img, mask, flow)
+    buf1 = torch.empty((B, 3, H, 4 * W), device=img.device, dtype=F32)
+    buf2 = torch.empty_like(buf1)
+    call('dmh_post_process', ptr(img), ptr(mask), ptr(flow), ptr(buf1), ptr(buf2), B, H, W)
+    return buf1, buf2
+
+
+def grid_shape(B, H, W, nrow=8, padding=2):
+    """torchvision's make_grid geometry for B images of (H, W): (sheet height, sheet width, xmaps); B == 1: the image alone"""
+    if B == 1:
+        return H, W, 1
+    xmaps = min(int(nrow), B)
+    ymaps = -(-B // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding, xmaps
+
+
+def preview_sheet(img, mask, flow, nrow=8, padding=2, bgr=True):
+    """the panels of post_process + channel swap + make_grid + save_image's quantisation in one launch: two uint8 (Hs, Ws, 3)
+    sheets on the device."""
+    B, H, W = _preview_inputs(img, mask, flow)
+    Hs, Ws, _ = grid_shape(B, H, 4 * W, nrow, padding)
+    s1 = torch.empty((Hs, Ws, 3), device=img.device, dtype=torch.uint8)
+    s2 = torch.empty_like(s1)
+    call('dmh_preview_sheet', ptr(img), ptr(mask), ptr(flow), ptr(s1, torch.uint8), ptr(s2, torch.uint8), B, H, W, int(nrow),
+         int(padding), int(bool(bgr)))
+    return s1, s2
+
+
+def homography_warp(src, homos, dsize):
+    """cv2.warpPerspective(src, M, dsize) without the inverse-map flag, exact bilinear (float64 coordinates and weights):
+    src (B,3,H,W) fp32, homos (B,3,3) f64, dsize = (width, height) as cv2 takes it -> (B,3,height,width)."""
+    B, C3, H, W = src.shape
+    assert C3 == 3 and homos.shape == (B, 3, 3), (src.shape, homos.shape)
+    Wd, Hd = int(dsize[0]), int(dsize[1])
+    dst = torch.empty((B, 3, Hd, Wd), device=src.device, dtype=F32)
+    call('dmh_homography_warp', ptr(src), ptr(homos, torch.float64), ptr(dst), B, H, W, Hd, Wd)
+    return dst
+
+
 # ------------------------------------------------------------------ training (SURVEY 8f row 1, first pieces)
 def conv_wgrad(dy, src0, src1=None, k=3, in_coef=None, want_bias=True, ups=0):
     """weight (and bias) gradient of the stride-1 kxk conv whose input was cat(src0, src1) (after the optional

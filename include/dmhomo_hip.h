@@ -506,6 +506,27 @@ int dmh_resize_bilinear_u8(const unsigned char* src, float* dst, int B, int Hs, 
 int dmh_mask_open_nearest(const float* src, float* dst, int B, int Hs, int Ws, int Hd, int Wd, int64_t dst_bstride,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * sample preview sheets (DDP:1489-1555; written by Trainer.train / Trainer.sample, DDP:1871-1935, 1972-2019)
+ * ------------------------------------------------------------------------------------- */
+/* postProcess DDP:1505-1517 in one launch: img [B][6][H][W], mask [B][1][H][W], flow [B][2][H][W] fp32 ->
+ * buf1 = [img1 | img1 | mask x3 | flow_vis], buf2 = [img2 | flow_warp(img2, flow) | mask x3 | flow_vis], each [B][3][H][4W].
+ * The warp panel is bit for bit the default (border, bilinear) flow warp above, the flow panel the flow-to-image kernel
+ * with max_flow = 256. */
+int dmh_post_process(const float* img, const float* mask, const float* flow, float* buf1, float* buf2, int B, int H, int W,
+                     void* stream);
+/* the same panels fused with the reference's channel swap [:, [2,1,0]] (bgr != 0), torchvision's make_grid(nrow, padding,
+ * pad_value = 0) and save_image's quantisation (x*255 + 0.5 in two roundings, clamp to [0, 255], truncate): two uint8
+ * sheets [Hs][Ws][3], 4-byte aligned.  xmaps = min(nrow, B), ymaps = ceil(B / xmaps), Hs = ymaps*(H+padding)+padding,
+ * Ws = xmaps*(4W+padding)+padding; B == 1: the image alone, Hs = H, Ws = 4W. */
+int dmh_preview_sheet(const float* img, const float* mask, const float* flow, unsigned char* sheet1, unsigned char* sheet2,
+                      int B, int H, int W, int nrow, int padding, int bgr, void* stream);
+/* cv2.warpPerspective(src, M, (Wd, Hd)) without the inverse-map flag (DDP:1527): src [B][3][H][W] fp32, homos [B][3][3]
+ * float64 -> dst [B][3][Hd][Wd], dst(x, y) = src(M^-1 (x, y, 1)), bilinear, constant border 0 per neighbour.  Deliberate
+ * deviation: the EXACT bilinear result (inverse, coordinates, weights in float64; one rounding to fp32), not cv2's
+ * fixed-point coefficient tables (fraction quantised to 1/32). */
+int dmh_homography_warp(const float* src, const double* homos, float* dst, int B, int H, int W, int Hd, int Wd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's training entry DGM/demo.py on dmhomo_amd.
 
-    python scripts/demo.py [-c <milestone>] [--data <CA-Homo Train dir>] [--steps N] [--image_size 256] [--bs 128]
+    python scripts/demo.py [-c <milestone>] [--data <CA-Homo Train dir>] [--steps N] [--image_size 256] [--bs 128] [--preview]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/demo.py ...
 
 Same model / diffusion / Trainer arguments as DEMO:15-58 (Unet dim 64, mults (1,2,4,8), 6 channels, 5 classes; l1,
@@ -10,7 +10,9 @@ pred_x0, 1000 steps; batch 128, lr 5e-4, accumulate 1, EMA 0.995).  Differences,
     (accelerate's split_batches=True, DDP:1717), gradients averaged with one RCCL all-reduce per step;
   * --data names the dataset directory (the reference hard-codes it, DDP:1058); without it the seeded synthetic
     conditions of dmhomo_amd.ddpm.SyntheticConditions are used;
-  * --steps overrides the 112 500 steps of DEMO:34-45 so that a smoke run ends.
+  * --steps overrides the 112 500 steps of DEMO:34-45 so that a smoke run ends;
+  * --preview turns on the sample sheets the reference always writes at every 1000th step (DDP:1871-1935:
+    results/sample-<m>-source.png / -target.png and a GIF); off by default.
 """
 import argparse
 import os
@@ -28,6 +30,7 @@ parser.add_argument('--steps', type=int, default=0)
 parser.add_argument('--image_size', type=int, default=256)          # DEMO:24
 parser.add_argument('--bs', type=int, default=256 // 2)             # DEMO:34
 parser.add_argument('--results', type=str, default='results')
+parser.add_argument('--preview', action='store_true', help='write sample sheets at every save_and_sample_every-th step')
 args = parser.parse_args()
 
 num_classes = 5
@@ -48,6 +51,7 @@ def main():
                       train_num_steps=args.steps or total, gradient_accumulate_every=1, ema_decay=0.995, amp=False,
                       results_folder=args.results, save_and_sample_every=1000, num_samples=9,
                       augment_horizontal_flip=False)
+    trainer.preview = args.preview
     if args.c != 0:
         trainer.load(args.c)
     trainer.train(log=(lambda s, l: print(f'step {s}: loss: {float(l):.4f}', flush=True)) if rank == 0 else None)

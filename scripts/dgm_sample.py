@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -9,6 +9,8 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
   * -c names results/model-<c>.pt like the reference; when the file does not exist the seeded random
     initialisation is used (the trained DGM.pt lives on HuggingFace, README:8);
   * the loop stops after --batches batches instead of running until killed (SAMPLE:62);
+  * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
+    generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
     still accepted and select the data slice exactly as the reference's unused arguments did: not at all); rank 0
     alone reads the checkpoint and broadcasts the online + EMA weights over RCCL (the reference's N processes each
@@ -46,6 +48,7 @@ parser.add_argument('-i', type=int, default=0)
 parser.add_argument('--image_size', type=int, default=256)        # SAMPLE:32 hard-codes 256
 parser.add_argument('--batches', type=int, default=2)
 parser.add_argument('--conditions', type=str, default=None)
+parser.add_argument('--preview', action='store_true', help='write preview sheets when the step counter is a multiple of 100')
 parser.add_argument('--seed', type=int, default=0, help='noise seed (every value is keyed by seed and global sample index)')
 args = parser.parse_args()
 
@@ -65,6 +68,7 @@ def main():
                       save_and_sample_every=2000, num_samples=4, augment_horizontal_flip=False, num_worker=0,
                       total_data_slice_idx=args.gpu_nums, data_slice_idx=args.i, shuffle=False,
                       split_batches=False)     # --bs is PER PROCESS, as for the reference's hand-started processes (SAMPLE:13-18)
+    trainer.preview = args.preview
     # rank 0 alone reads the checkpoint; the online and the EMA copy reach the other ranks as one RCCL payload each
     have = os.path.exists(os.path.join('results', f'model-{args.c}.pt')) if rank == 0 else None
     if not D.load_on_rank0_and_broadcast(trainer, args.c if have else None):
