@@ -12,7 +12,6 @@ from torch import nn
 
 from . import _params as P
 from . import ops
-from ._lib import DmhStep
 from .engine import UnetEngine
 from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
 from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
@@ -173,9 +172,8 @@ class Unet(nn.Module):
             raise TypeError("forward() got multiple values for keyword argument 'cond_drop_prob'")   # as CFG:409 would
         x, time, classes, rgb_flow, mask = _bind_forward(self.forward, args, kwargs)
         logits, null, computed = self._cond_null(x, time, classes, rgb_flow, mask)
-        step = DmhStep(objective=ops.OBJECTIVE['pred_x0'], clip=0, mode=ops.MODE_LAST, cond_scale=float(cond_scale),
-                       sqrt_recip_ac=1., sqrt_recipm1_ac=1.)
-        out, _, _ = ops.sampler_step(step, logits, null, null, None, want_x_start=False, keep=computed)
+        out, _, _ = ops.sampler_step(ScheduleHost._blend_step(cond_scale), logits, null, null, None, want_x_start=False,
+                                     keep=computed)
         return out
 
 
@@ -193,23 +191,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                  objective='pred_noise', beta_schedule='cosine', p2_loss_weight_gamma=0., p2_loss_weight_k=1,
                  ddim_sampling_eta=1.):
         super().__init__()
-        assert not (type(self) == GaussianDiffusion and model.channels != model.out_dim)
-        assert not model.random_or_learned_sinusoidal_cond
-        self.model = model
-        self.channels = self.model.channels
-        self.image_size = image_size
-        self.objective = objective
-        assert objective in {'pred_noise', 'pred_x0', 'pred_v'}, \
-            'objective must be either pred_noise (predict noise) or pred_x0 (predict image start) or pred_v (predict v)'
-        bufs = make_buffers(beta_schedule, timesteps, p2_loss_weight_gamma, p2_loss_weight_k)
-        self.num_timesteps = int(bufs['betas'].shape[0])
-        self.loss_type = loss_type
-        self.sampling_timesteps = default(sampling_timesteps, timesteps)
-        assert self.sampling_timesteps <= timesteps
-        self.is_ddim_sampling = self.sampling_timesteps < timesteps
-        self.ddim_sampling_eta = ddim_sampling_eta
-        for name, val in bufs.items():
-            self.register_buffer(name, val)
+        self._init_diffusion(model, image_size, timesteps, sampling_timesteps, loss_type, objective, beta_schedule,
+                             p2_loss_weight_gamma, p2_loss_weight_k, ddim_sampling_eta)
 
     @property
     def rng(self):
@@ -233,9 +216,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         t0 = self._uniform_time(t)
         if t0 is None:
             if null is not None:                             # null + (cond - null) * cond_scale, CFG:410
-                blend = DmhStep(objective=ops.OBJECTIVE['pred_x0'], clip=0, mode=ops.MODE_LAST,
-                                cond_scale=float(cond_scale), sqrt_recip_ac=1., sqrt_recipm1_ac=1.)
-                cond, _, _ = ops.sampler_step(blend, cond, null, null, None, want_x_start=False, keep=computed)
+                cond, _, _ = ops.sampler_step(self._blend_step(cond_scale), cond, null, null, None, want_x_start=False,
+                                              keep=computed)
             return self._predictions_per_row(cond, x.contiguous(), t, clip_x_start)
         step = self._step(host, t0, ops.MODE_LAST, clip_x_start, cond_scale=cond_scale)
         _, x_start, pred_noise = ops.sampler_step(step, cond, null, x.contiguous(), None, True, True, keep=computed)
@@ -357,20 +339,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         raise TypeError('classifier_free_guidance.GaussianDiffusion.interpolate is not callable in the reference '
                         '(CFG:733 vs CFG:639); use denoising_diffusion_pytorch.GaussianDiffusion.interpolate')
 
-    def q_sample(self, x_start, t, noise=None):
-        """CFG:738-742."""
-        noise = default(noise, lambda: self.rng.randn(x_start.shape, x_start.device))
-        ca = self.sqrt_alphas_cumprod.gather(-1, t).contiguous()
-        cb = self.sqrt_one_minus_alphas_cumprod.gather(-1, t).contiguous()
-        return ops.q_sample(x_start.contiguous(), noise.contiguous(), ca, cb)
-
-    @property
-    def loss_fn(self):
-        """CFG:744-751 — the name of the elementwise loss (the reduction runs in dmh_diff_mean)."""
-        if self.loss_type in ('l1', 'l2'):
-            return self.loss_type
-        raise ValueError(f'invalid loss type {self.loss_type}')
-
     @torch.no_grad()
     def p_losses(self, x_start, t, *, classes, rgb_flow, flow, mask, noise=None):
         """CFG:770-806, the loss VALUE: q_sample -> UNet (class dropout p=0.5) -> flow_warp -> L1/L2 + alpha_bar_t-weighted
@@ -386,16 +354,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         model_out = self.model(x, t, classes, rgb_flow=rgb_flow, mask=mask)
         im1, im2 = model_out[:, :3].contiguous(), model_out[:, 3:].contiguous()
         im2_warp = flow_warp(im2, flow)
-        if self.objective == 'pred_noise':
-            target = noise
-        elif self.objective == 'pred_x0':
-            target = x_start
-        elif self.objective == 'pred_v':                         # predict_v, CFG:596-598
-            ca = self.sqrt_alphas_cumprod.gather(-1, t).contiguous()
-            cb = (-self.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous()
-            target = ops.q_sample(noise, x_start, ca, cb)
-        else:
-            raise ValueError(f'unknown objective {self.objective}')
+        target = self._loss_target(x_start, t, noise)
         loss = ops.diff_mean(model_out, target, None, squared)
         photo = ops.diff_mean(im2_warp, im1, mask.to(torch.float32).contiguous(), squared)
         w = self.alphas_cumprod.gather(-1, t).contiguous()

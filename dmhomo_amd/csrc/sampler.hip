@@ -132,104 +132,85 @@ __global__ __launch_bounds__(256) void final_conv_kernel(const float* __restrict
 // torch.clamp(x, -1., 1.) (CFG:612,634): NaN stays NaN (fminf / fmaxf alone would turn it into -1 and hide a broken row)
 __device__ __forceinline__ float clamp_pm1(float x) { return x != x ? x : fminf(fmaxf(x, -1.f), 1.f); }
 
-__global__ __launch_bounds__(256) void sampler_step_kernel(DmhStep s, const float* __restrict__ mc,
-                                                           const float* __restrict__ mn, const float* __restrict__ x,
-                                                           const float* __restrict__ noise, float* __restrict__ img_out,
-                                                           float* __restrict__ x_start, float* __restrict__ pred_noise,
-                                                           int64_t n, const uint8_t* __restrict__ keep, int64_t per_row) {
+// the network output a step works on: model_cond[i], or with model_null the guided null + (cond - null) * cond_scale (CFG:410).
+// keep (with model_null): row i / per_row of model_cond was only computed where keep != 0 — a row whose class the conditional
+// pass dropped (CFG:415-425) has the null pass's inputs, so its logits ARE the null logits and model_cond is never read there
+__device__ __forceinline__ float guided_logit(const float* mc, const float* mn, const uint8_t* keep, int64_t i, int64_t per_row,
+                                              float cond_scale) {
+  if (!mn) return mc[i];
+  const float nl = mn[i];
+  const float mo = (keep && !keep[i / per_row]) ? nl : mc[i];
+  return nl + (mo - nl) * cond_scale;
+}
+
+// ONE denoise step on one element, the only statement of it: every step kernel below calls this, so the eager, the captured
+// and the fused path cannot differ in a bit.  mo: guided_logit, xt: the current image, nz: the entry's noise value, has_noise:
+// whether the DDPM update adds it (a DDIM update always does) -> x0 (x_start), pn (pred_noise), o (the next image)
+__device__ __forceinline__ void denoise_step(const DmhStep& s, float mo, float xt, float nz, bool has_noise, float& x0,
+                                             float& pn, float& o) {
+  if (s.objective == 0) {  // pred_noise, CFG:614-617
+    pn = mo;
+    x0 = s.sqrt_recip_ac * xt - s.sqrt_recipm1_ac * pn;
+    if (s.clip) x0 = clamp_pm1(x0);
+  } else if (s.objective == 1) {  // pred_x0, CFG:619-622
+    x0 = mo;
+    if (s.clip) x0 = clamp_pm1(x0);
+    pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
+  } else {  // pred_v, CFG:624-628
+    x0 = s.sqrt_ac * xt - s.sqrt_1m_ac * mo;
+    if (s.clip) x0 = clamp_pm1(x0);
+    pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
+  }
+  if (s.mode == 0) {  // DDIM, CFG:705-707
+    o = x0 * s.c0 + s.c1 * pn + s.c2 * nz;
+  } else if (s.mode == 1) {  // last DDIM step, CFG:693-695
+    o = x0;
+  } else {  // DDPM posterior step, DDP:604-611,660: mean + exp(.5 logvar) * noise (no noise at t == 0)
+    o = s.c0 * x0 + s.c1 * xt;
+    if (has_noise) o = o + s.c2 * nz;
+  }
+}
+
+// the body of the two element-per-thread step kernels.  missing: what stands for the noise of an entry that has none
+__device__ __forceinline__ void sampler_step_body(const DmhStep& s, const float* mc, const float* mn, const float* x,
+                                                  const float* noise, float* img_out, float* x_start, float* pred_noise,
+                                                  int64_t n, const uint8_t* keep, int64_t per_row, float missing) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float mo;
-    if (mn) {
-      // keep (with model_null): row i / per_row of model_cond was only computed where keep != 0 — a row whose class the
-      // conditional pass dropped (CFG:415-425) has the null pass's inputs, so its logits ARE the null logits
-      const float nl = mn[i];
-      mo = (keep && !keep[i / per_row]) ? nl : mc[i];
-      mo = nl + (mo - nl) * s.cond_scale;  // CFG:410
-    } else {
-      mo = mc[i];
-    }
-    const float xt = x[i];
-    float x0, pn;
-    if (s.objective == 0) {  // pred_noise, CFG:614-617
-      pn = mo;
-      x0 = s.sqrt_recip_ac * xt - s.sqrt_recipm1_ac * pn;
-      if (s.clip) x0 = clamp_pm1(x0);
-    } else if (s.objective == 1) {  // pred_x0, CFG:619-622
-      x0 = mo;
-      if (s.clip) x0 = clamp_pm1(x0);
-      pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-    } else {  // pred_v, CFG:624-628
-      x0 = s.sqrt_ac * xt - s.sqrt_1m_ac * mo;
-      if (s.clip) x0 = clamp_pm1(x0);
-      pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-    }
-    float o;
-    if (s.mode == 0) {  // DDIM, CFG:705-707
-      o = x0 * s.c0 + s.c1 * pn + s.c2 * noise[i];
-    } else if (s.mode == 1) {  // last DDIM step, CFG:693-695
-      o = x0;
-    } else {  // DDPM posterior step, DDP:604-611,660: mean + exp(.5 logvar) * noise (noise == NULL at t == 0)
-      o = s.c0 * x0 + s.c1 * xt;
-      if (noise) o = o + s.c2 * noise[i];
-    }
+    const float mo = guided_logit(mc, mn, keep, i, per_row, s.cond_scale);
+    const float nz = (noise && s.mode != 1) ? noise[i] : missing;
+    float x0, pn, o;
+    denoise_step(s, mo, x[i], nz, noise != nullptr, x0, pn, o);
     img_out[i] = o;
     if (x_start) x_start[i] = x0;
     if (pred_noise) pred_noise[i] = pn;
   }
 }
 
+// (a DDIM step without noise is refused at launch: `missing` is never read)
+__global__ __launch_bounds__(256) void sampler_step_kernel(DmhStep s, const float* __restrict__ mc,
+                                                           const float* __restrict__ mn, const float* __restrict__ x,
+                                                           const float* __restrict__ noise, float* __restrict__ img_out,
+                                                           float* __restrict__ x_start, float* __restrict__ pred_noise,
+                                                           int64_t n, const uint8_t* __restrict__ keep, int64_t per_row) {
+  sampler_step_body(s, mc, mn, x, noise, img_out, x_start, pred_noise, n, keep, per_row, 0.f);
+}
+
 // the step kernel with its DmhStep read from device memory (dmh_sampler_step_dev); no __restrict__ on x / img_out: the
-// replayed loop updates img in place (every element is read by the thread that writes it)
+// replayed loop updates img in place (every element is read by the thread that writes it).  A DDIM entry always comes with
+// noise; the device-resident entry cannot be checked at launch, so a mis-sequenced cursor (the last-step graph replayed on a
+// non-last entry) shows up as NaN instead of a plausible wrong sample
 __global__ __launch_bounds__(256) void sampler_step_dev_kernel(const DmhStep* __restrict__ sp, const float* __restrict__ mc,
                                                                const float* __restrict__ mn, const float* x,
                                                                const float* __restrict__ noise, float* img_out,
                                                                float* __restrict__ x_start, float* __restrict__ pred_noise,
                                                                int64_t n, const uint8_t* __restrict__ keep, int64_t per_row) {
   const DmhStep s = *sp;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float mo;
-    if (mn) {
-      const float nl = mn[i];
-      mo = (keep && !keep[i / per_row]) ? nl : mc[i];   // (as sampler_step_kernel)
-      mo = nl + (mo - nl) * s.cond_scale;  // CFG:410
-    } else {
-      mo = mc[i];
-    }
-    const float xt = x[i];
-    float x0, pn;
-    if (s.objective == 0) {
-      pn = mo;
-      x0 = s.sqrt_recip_ac * xt - s.sqrt_recipm1_ac * pn;
-      if (s.clip) x0 = clamp_pm1(x0);
-    } else if (s.objective == 1) {
-      x0 = mo;
-      if (s.clip) x0 = clamp_pm1(x0);
-      pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-    } else {
-      x0 = s.sqrt_ac * xt - s.sqrt_1m_ac * mo;
-      if (s.clip) x0 = clamp_pm1(x0);
-      pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-    }
-    float o;
-    if (s.mode == 0) {
-      // a DDIM entry always comes with noise; the device-resident entry cannot be checked at launch, so a mis-sequenced
-      // cursor (the last-step graph replayed on a non-last entry) shows up as NaN instead of a plausible wrong sample
-      o = x0 * s.c0 + s.c1 * pn + s.c2 * (noise ? noise[i] : __builtin_nanf(""));
-    } else if (s.mode == 1) {
-      o = x0;
-    } else {
-      o = s.c0 * x0 + s.c1 * xt;
-      if (noise) o = o + s.c2 * noise[i];
-    }
-    img_out[i] = o;
-    if (x_start) x_start[i] = x0;
-    if (pred_noise) pred_noise[i] = pn;
-  }
+  sampler_step_body(s, mc, mn, x, noise, img_out, x_start, pred_noise, n, keep, per_row, __builtin_nanf(""));
 }
 
-// dmh_sampler_step_ddp_dev: the replayed step of the unconditional loop (DDP:647-729) in one pass — the step of
-// sampler_step_dev_kernel (same operations, same order, model_null absent), its noise drawn here from the sample-indexed
-// generator (the values rng_indexed_kernel would have stored; never stored) or read from `noise`, and the next step's network
+// dmh_sampler_step_ddp_dev: the replayed step of the unconditional loop (DDP:647-729) in one pass — denoise_step on the entry
+// in device memory (model_null absent), its noise drawn here from the sample-indexed generator (the values
+// rng_indexed_kernel would have stored; never stored) or read from `noise`, and the next step's network
 // input written as dmh_assemble_input writes it.  One thread per P pixels of a row and every channel: P = 4 when HW % 4 == 0,
 // where the 4 pixels of one channel are exactly one Philox counter quad; P = 1 otherwise (a thread then draws its element's
 // quad and keeps one lane).  The channel loop is not unrolled and no array is indexed by a runtime value (no scratch).
@@ -287,30 +268,8 @@ __global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __
       }
 #pragma unroll
       for (int j = 0; j < P; ++j) {
-        const float m = mo[j], x = xt[j];
-        float x0, pn;
-        if (s.objective == 0) {
-          pn = m;
-          x0 = s.sqrt_recip_ac * x - s.sqrt_recipm1_ac * pn;
-          if (s.clip) x0 = clamp_pm1(x0);
-        } else if (s.objective == 1) {
-          x0 = m;
-          if (s.clip) x0 = clamp_pm1(x0);
-          pn = (s.sqrt_recip_ac * x - x0) / s.sqrt_recipm1_ac;
-        } else {
-          x0 = s.sqrt_ac * x - s.sqrt_1m_ac * m;
-          if (s.clip) x0 = clamp_pm1(x0);
-          pn = (s.sqrt_recip_ac * x - x0) / s.sqrt_recipm1_ac;
-        }
-        float o;
-        if (s.mode == 0) {
-          o = x0 * s.c0 + s.c1 * pn + s.c2 * nz[j];
-        } else if (s.mode == 1) {
-          o = x0;
-        } else {
-          o = s.c0 * x0 + s.c1 * x;
-          if (drawn) o = o + s.c2 * nz[j];
-        }
+        float x0, pn, o;
+        denoise_step(s, mo[j], xt[j], nz[j], drawn, x0, pn, o);
         img[base + j] = o;
         if (x_start) x_start[base + j] = x0;
         if (xo) {   // cat((x_start, img)) with self-conditioning, img alone without (DDP:411), NHWC

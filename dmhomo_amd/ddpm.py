@@ -54,11 +54,7 @@ class Unet(nn.Module):
         eng.ensure_prepared()
         x = x.to(torch.float32).contiguous()
         time = time.to(torch.int64).contiguous()
-        if self.self_condition:
-            sc = default(x_self_cond, lambda: torch.zeros_like(x)).to(torch.float32).contiguous()
-            xin = ops.assemble_input(sc, x, None, cpad=eng.cin_pad)          # cat((x_self_cond, x)), DDP:411
-        else:
-            xin = ops.assemble_input(x, None, None, cpad=eng.cin_pad)
+        xin = ops.uncond_input(x, x_self_cond, self.self_condition, eng.cin_pad)
         cond = eng.embed(time, None, 1)
         return eng.trunk(eng.stem(xin), cond)
 
@@ -70,24 +66,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                  objective='pred_noise', beta_schedule='cosine', p2_loss_weight_gamma=0., p2_loss_weight_k=1,
                  ddim_sampling_eta=1.):
         super().__init__()
-        assert not (type(self) == GaussianDiffusion and model.channels != model.out_dim)
-        assert not model.random_or_learned_sinusoidal_cond
-        self.model = model
-        self.channels = self.model.channels
+        self._init_diffusion(model, image_size, timesteps, sampling_timesteps, loss_type, objective, beta_schedule,
+                             p2_loss_weight_gamma, p2_loss_weight_k, ddim_sampling_eta)
         self.self_condition = self.model.self_condition
-        self.image_size = image_size
-        self.objective = objective
-        assert objective in {'pred_noise', 'pred_x0', 'pred_v'}, \
-            'objective must be either pred_noise (predict noise) or pred_x0 (predict image start) or pred_v (predict v)'
-        bufs = make_buffers(beta_schedule, timesteps, p2_loss_weight_gamma, p2_loss_weight_k)
-        self.num_timesteps = int(bufs['betas'].shape[0])
-        self.loss_type = loss_type
-        self.sampling_timesteps = default(sampling_timesteps, timesteps)
-        assert self.sampling_timesteps <= timesteps
-        self.is_ddim_sampling = self.sampling_timesteps < timesteps
-        self.ddim_sampling_eta = ddim_sampling_eta
-        for name, val in bufs.items():
-            self.register_buffer(name, val)
         self.rng = DeviceRng()
 
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False):
@@ -221,10 +202,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
         def fill(st):
             st['img'].copy_(rng.randn(shape, device))        # DDP:668 / DDP:696
-            if sc:                                           # the first step's self-condition is zeros (DDP:410-411)
-                ops.assemble_input(st['zeros'], st['img'], None, cpad=st['xin'].shape[3], out=st['xin'])
-            else:
-                ops.assemble_input(st['img'], None, None, cpad=st['xin'].shape[3], out=st['xin'])
+            # (the first step's self-condition is zeros, DDP:410-411: the preallocated ones, nothing is allocated here)
+            ops.uncond_input(st['img'], st['zeros'], sc, st['xin'].shape[3], out=st['xin'])
         return self._replay_captured(shape, device, key, lambda: self._graph_tables(kind, clip), buffers, fill)
 
     @torch.no_grad()
@@ -249,20 +228,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             img, _ = self.p_sample(img, i)
         return img
 
-    def q_sample(self, x_start, t, noise=None):
-        """DDP:756-761."""
-        noise = default(noise, lambda: self.rng.randn(x_start.shape, x_start.device))
-        ca = self.sqrt_alphas_cumprod.gather(-1, t).contiguous()
-        cb = self.sqrt_one_minus_alphas_cumprod.gather(-1, t).contiguous()
-        return ops.q_sample(x_start.contiguous(), noise.contiguous(), ca, cb)
-
-    @property
-    def loss_fn(self):
-        """DDP:763-770 — the name of the elementwise loss (the reduction runs in dmh_diff_mean)."""
-        if self.loss_type in ('l1', 'l2'):
-            return self.loss_type
-        raise ValueError(f'invalid loss type {self.loss_type}')
-
     _random = staticmethod(__import__('random').random)      # the `random() < 0.5` self-conditioning draw of DDP:785
 
     def p_losses(self, x_start, t, noise=None):
@@ -275,25 +240,6 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             return ddp_loss_with_grad_fn(self, x_start, t, noise)
         with torch.no_grad():
             return self._p_losses_value(x_start, t, noise)
-
-    def _pred_x_start(self, x, t, model_out):
-        """model_predictions(x, t, ...).pred_x_start for a given UNet output (DDP:582-600, no clamp): per-sample
-        coefficients, t differs from row to row"""
-        if self.objective == 'pred_x0':
-            return model_out
-        ca = (self.sqrt_recip_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_alphas_cumprod)
-        cb = (self.sqrt_recipm1_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_one_minus_alphas_cumprod)
-        return ops.q_sample(x, model_out.contiguous(), ca.gather(-1, t).contiguous(), (-cb).gather(-1, t).contiguous())
-
-    def _loss_target(self, x_start, t, noise):
-        if self.objective == 'pred_noise':
-            return noise
-        if self.objective == 'pred_x0':
-            return x_start
-        if self.objective == 'pred_v':                       # predict_v, DDP:596-598
-            return ops.q_sample(noise, x_start, self.sqrt_alphas_cumprod.gather(-1, t).contiguous(),
-                                (-self.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous())
-        raise ValueError(f'unknown objective {self.objective}')
 
     def _p_losses_value(self, x_start, t, noise=None):
         """DDP:772-811, forward value only"""

@@ -61,7 +61,7 @@ def f16x3_default():
 
 def _batchable(kh, stride, upsample2):
     # (dmh_pack_conv_weights_multi makes the fp16-piece images of the default kernels only)
-    return kh in (1, 3) and stride == 1 and not upsample2 and os.environ.get('DMH_CONV3_VARIANT', '9') == '9'
+    return kh in (1, 3) and stride == 1 and not upsample2 and f16x3_default()
 
 
 class PackedConv:
@@ -187,15 +187,20 @@ def conv2d(pc, src0, src1=None, in_coef=None, res=None, res_coef=None, want_stat
 
 
 # ------------------------------------------------------------------ normalisation glue
+def _ss_arg(ss, B, Cc):
+    """(pointer, row stride) of the (scale, shift) rows: ss is None, or a (B, 2C) view with unit column stride"""
+    if ss is None:
+        return None, 0
+    assert ss.stride(1) == 1 and ss.shape[0] == B and ss.shape[1] == 2 * Cc
+    return C.c_void_p(ss.data_ptr()), ss.stride(0)
+
+
 def gn_finalize(stats, gamma, beta, hw, groups, ss=None, eps=1e-5, want_bound=False, rows=None):
     """N2: stats (B,tiles,C,2) -> coef (B,2,C).  ss: (B, >=2C) view whose row b starts with (scale[C], shift[C]).
     want_bound: -> (coef, bound) with bound (B, groups) >= |a*x + b| over each (sample, group): ``conv2d(in_bound=)``."""
     B, tiles, Cc, _ = stats.shape
     coef = _empty((B, 2, Cc), stats)
-    ss_ptr, ss_stride = None, 0
-    if ss is not None:
-        assert ss.stride(1) == 1 and ss.shape[0] == B and ss.shape[1] == 2 * Cc
-        ss_ptr, ss_stride = C.c_void_p(ss.data_ptr()), ss.stride(0)
+    ss_ptr, ss_stride = _ss_arg(ss, B, Cc)
     if want_bound:
         bound = _empty((B, groups), stats)
         call('dmh_gn_finalize_bound', ptr(stats), tiles, ptr(gamma), ptr(beta), ss_ptr, ss_stride, ptr(coef), ptr(bound),
@@ -375,6 +380,15 @@ def assemble_input(a, b=None, m=None, reps=1, cpad=None, out=None):
         raise ValueError(f'assemble_input: out has shape {tuple(out.shape)}, expected {(reps * B, H, W, cpad)}')
     call('dmh_assemble_input', ptr(a), ca, ptr(b), cb, ptr(m), ptr(out), B, reps, H * W, cpad)
     return out
+
+
+def uncond_input(x, x_self_cond, self_condition, cpad, out=None):
+    """the network input of ddpm.Unet (DDP:408-411), NHWC: cat((x_self_cond, x)) when the model self-conditions — zeros for a
+    self-condition that is not given — else x alone.  x: contiguous fp32 (B,C,H,W)."""
+    if not self_condition:
+        return assemble_input(x, None, None, cpad=cpad, out=out)
+    sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.to(F32).contiguous()
+    return assemble_input(sc, x, None, cpad=cpad, out=out)
 
 
 def final_conv_nchw(x, w, bias):
@@ -723,10 +737,7 @@ def gn_finalize_train(stats, gamma, beta, hw, groups, ss=None, eps=1e-5):
     B, tiles, Cc, _ = stats.shape
     coef = _empty((B, 2, Cc), stats)
     mr = _empty((B, groups, 2), stats)
-    ss_ptr, ss_stride = None, 0
-    if ss is not None:
-        assert ss.stride(1) == 1 and ss.shape[0] == B and ss.shape[1] == 2 * Cc
-        ss_ptr, ss_stride = C.c_void_p(ss.data_ptr()), ss.stride(0)
+    ss_ptr, ss_stride = _ss_arg(ss, B, Cc)
     call('dmh_gn_finalize_train', ptr(stats), tiles, ptr(gamma), ptr(beta), ss_ptr, ss_stride, ptr(coef), ptr(mr), B, Cc,
          groups, hw, float(eps))
     return coef, mr
@@ -741,10 +752,7 @@ def gn_silu_backward(dout, y, coef, mr, gamma, beta, groups, ss=None):
     pg = _empty((B, 4, Cc), y)
     part = _empty((B, lib().dmh_gn_bwd_chunks(hw), Cc, 2), y)
     bcoef = _empty((B, 3, Cc), y)
-    ss_ptr, ss_stride = None, 0
-    if ss is not None:
-        assert ss.stride(1) == 1 and ss.shape[0] == B and ss.shape[1] == 2 * Cc
-        ss_ptr, ss_stride = C.c_void_p(ss.data_ptr()), ss.stride(0)
+    ss_ptr, ss_stride = _ss_arg(ss, B, Cc)
     call('dmh_gn_silu_backward', ptr(dout), ptr(y), ptr(coef), ptr(mr), ptr(gamma), ptr(beta), ss_ptr, ss_stride, ptr(dy),
          ptr(pg), ptr(part), ptr(bcoef), B, hw, Cc, groups)
     # pg is (B, 4, C): per sample (dgamma, dbeta, dscale, dshift) parts.  All four are summed over the batch in place (the

@@ -7,7 +7,7 @@ import torch
 
 from . import ops
 from ._lib import DmhStep
-from .schedule import ddim_pairs
+from .schedule import ddim_pairs, make_buffers
 
 ModelPrediction = namedtuple('ModelPrediction', ['pred_noise', 'pred_x_start'])
 
@@ -105,9 +105,67 @@ class DeviceRng:
 
 
 class ScheduleHost:
-    """host mirrors of the schedule buffers: the reference indexes device buffers with python ints and does
-    0-dim fp32 tensor arithmetic on them (CFG:697-701); here the same ops run on CPU copies and the results
-    enter the sampler kernel as scalars (``DmhStep``).  Also the replayed sampling loop both diffusion classes share."""
+    """what the two GaussianDiffusion classes share.  The constructor body, q_sample, the loss target.  Host mirrors of the
+    schedule buffers: the reference indexes device buffers with python ints and does 0-dim fp32 tensor arithmetic on them
+    (CFG:697-701); here the same ops run on CPU copies and the results enter the sampler kernel as scalars (``DmhStep``).
+    And the replayed sampling loop."""
+
+    def _init_diffusion(self, model, image_size, timesteps, sampling_timesteps, loss_type, objective, beta_schedule,
+                        p2_loss_weight_gamma, p2_loss_weight_k, ddim_sampling_eta):
+        """the body of GaussianDiffusion.__init__, CFG:500-584 [DDP:483-582]; buffers and their names as the reference"""
+        # (``type(self) == GaussianDiffusion`` in the reference: the two classes are the direct subclasses of this one)
+        assert not (ScheduleHost in type(self).__bases__ and model.channels != model.out_dim)
+        assert not model.random_or_learned_sinusoidal_cond
+        self.model = model
+        self.channels = self.model.channels
+        self.image_size = image_size
+        self.objective = objective
+        assert objective in {'pred_noise', 'pred_x0', 'pred_v'}, \
+            'objective must be either pred_noise (predict noise) or pred_x0 (predict image start) or pred_v (predict v)'
+        bufs = make_buffers(beta_schedule, timesteps, p2_loss_weight_gamma, p2_loss_weight_k)
+        self.num_timesteps = int(bufs['betas'].shape[0])
+        self.loss_type = loss_type
+        self.sampling_timesteps = default(sampling_timesteps, timesteps)
+        assert self.sampling_timesteps <= timesteps
+        self.is_ddim_sampling = self.sampling_timesteps < timesteps
+        self.ddim_sampling_eta = ddim_sampling_eta
+        for name, val in bufs.items():
+            self.register_buffer(name, val)
+
+    def q_sample(self, x_start, t, noise=None):
+        """CFG:738-742 [DDP:756-761]."""
+        noise = default(noise, lambda: self.rng.randn(x_start.shape, x_start.device))
+        ca = self.sqrt_alphas_cumprod.gather(-1, t).contiguous()
+        cb = self.sqrt_one_minus_alphas_cumprod.gather(-1, t).contiguous()
+        return ops.q_sample(x_start.contiguous(), noise.contiguous(), ca, cb)
+
+    @property
+    def loss_fn(self):
+        """CFG:744-751 [DDP:763-770] — the name of the elementwise loss (the reduction runs in dmh_diff_mean)."""
+        if self.loss_type in ('l1', 'l2'):
+            return self.loss_type
+        raise ValueError(f'invalid loss type {self.loss_type}')
+
+    def _pred_x_start(self, x, t, model_out):
+        """model_predictions(x, t, ...).pred_x_start for a given UNet output (DDP:582-600, no clamp): per-sample
+        coefficients, t differs from row to row"""
+        if self.objective == 'pred_x0':
+            return model_out
+        ca = (self.sqrt_recip_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_alphas_cumprod)
+        cb = (self.sqrt_recipm1_alphas_cumprod if self.objective == 'pred_noise' else self.sqrt_one_minus_alphas_cumprod)
+        return ops.q_sample(x, model_out.contiguous(), ca.gather(-1, t).contiguous(), (-cb).gather(-1, t).contiguous())
+
+    def _loss_target(self, x_start, t, noise):
+        """what the UNet output is compared with (CFG:786-794 [DDP:795-803]): the one statement of it, for the loss value
+        of both classes and both training steps"""
+        if self.objective == 'pred_noise':
+            return noise
+        if self.objective == 'pred_x0':
+            return x_start
+        if self.objective == 'pred_v':                       # predict_v, CFG:596-598
+            return ops.q_sample(noise, x_start, self.sqrt_alphas_cumprod.gather(-1, t).contiguous(),
+                                (-self.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous())
+        raise ValueError(f'unknown objective {self.objective}')
 
     _HOST_NAMES = ('alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'sqrt_alphas_cumprod',
                    'sqrt_one_minus_alphas_cumprod', 'posterior_mean_coef1', 'posterior_mean_coef2',
@@ -187,6 +245,12 @@ class ScheduleHost:
                        sqrt_ac=float(host['sqrt_alphas_cumprod'][t]),
                        sqrt_1m_ac=float(host['sqrt_one_minus_alphas_cumprod'][t]),
                        c0=float(c[0]), c1=float(c[1]), c2=float(c[2]))
+
+    @staticmethod
+    def _blend_step(cond_scale):
+        """the guidance blend alone, null + (cond - null) * cond_scale (CFG:410), as a step: the logits pass through as x0"""
+        return DmhStep(objective=ops.OBJECTIVE['pred_x0'], clip=0, mode=ops.MODE_LAST, cond_scale=float(cond_scale),
+                       sqrt_recip_ac=1., sqrt_recipm1_ac=1.)
 
     def _ddim_coef(self, host, time, time_next):
         """sqrt(alpha_next), c, sigma in the reference's op order, CFG:697-701."""

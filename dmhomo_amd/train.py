@@ -14,7 +14,7 @@ csrc/norm_backward.hip:
 whole conditional UNet (CFG:412-466) with a manual tape; ``TrainStep`` adds p_losses (CFG:770-806) with its gradient,
 gradient accumulation, the global-norm clip, Adam and the RCCL gradient all-reduce: one optimiser step of
 ``Trainer.train`` (DDP:1830-1862).  ``DDPTrainStep`` does the same for the unconditional ddpm.GaussianDiffusion (DDP:772-820)
-on the same UnetTrain.  There is no autograd anywhere on this path; ``_PLoss`` / ``_PLossDDP`` hand the finished gradients
+on the same UnetTrain.  There is no autograd anywhere on this path; ``_PLoss`` hands the finished gradients
 to autograd when a user calls ``loss.backward()``.
 """
 import os
@@ -272,16 +272,15 @@ class UnetTrain:
             o, n2 = n.ss_off, 2 * n.cout
             g[n.keys['mlp_w']], g[n.keys['mlp_b']] = dw[o:o + n2].contiguous(), db[o:o + n2].contiguous()
         dcond = ops.act(sv['cond'], 'silu', dy=dac)
-        if self.uncond:
-            da1, g['time_mlp.3.weight'], g['time_mlp.3.bias'] = ops.linear_backward(sv['a1'], sd['time_mlp.3.weight'], dcond)
-            dh1 = ops.act(sv['h1'], 'gelu', dy=da1)
-            _, g['time_mlp.1.weight'], g['time_mlp.1.bias'] = ops.linear_backward(sv['se'], sd['time_mlp.1.weight'], dh1)
-            return
         td = sd['time_mlp.3.weight'].shape[0]
-        dtemb, dcemb = dcond[:, :td].contiguous(), dcond[:, td:].contiguous()
+        # DDP:417: the conditioning is the time embedding alone; CFG:436-441: cat(time, class) embeddings
+        dtemb = dcond if self.uncond else dcond[:, :td].contiguous()
         da1, g['time_mlp.3.weight'], g['time_mlp.3.bias'] = ops.linear_backward(sv['a1'], sd['time_mlp.3.weight'], dtemb)
         dh1 = ops.act(sv['h1'], 'gelu', dy=da1)
         _, g['time_mlp.1.weight'], g['time_mlp.1.bias'] = ops.linear_backward(sv['se'], sd['time_mlp.1.weight'], dh1)
+        if self.uncond:
+            return
+        dcemb = dcond[:, td:].contiguous()
         da2, g['classes_mlp.2.weight'], g['classes_mlp.2.bias'] = ops.linear_backward(sv['a2'], sd['classes_mlp.2.weight'], dcemb)
         dh2 = ops.act(sv['h2'], 'gelu', dy=da2)
         dce, g['classes_mlp.0.weight'], g['classes_mlp.0.bias'] = ops.linear_backward(sv['ce'], sd['classes_mlp.0.weight'], dh2)
@@ -306,11 +305,7 @@ class UnetTrain:
         assert self.uncond, 'forward_uncond is the ddpm.Unet forward; this UnetTrain holds a conditional Unet'
         x = x.to(torch.float32).contiguous()
         ss_all, emb = self._embed_forward(time.to(torch.int64).contiguous(), None, None)
-        if self.module.self_condition:                           # the input is cat(x_self_cond, x), DDP:411
-            sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.to(torch.float32).contiguous()
-            xin = ops.assemble_input(sc, x, None, cpad=self.cin_pad)
-        else:
-            xin = ops.assemble_input(x, None, None, cpad=self.cin_pad)
+        xin = ops.uncond_input(x, x_self_cond, self.module.self_condition, self.cin_pad)
         return self._trunk_forward(xin, ss_all, emb, taps)
 
     def _trunk_forward(self, xin, ss_all, emb, taps=None):
@@ -479,16 +474,7 @@ class TrainStep:
         x = df.q_sample(x_start, t, noise)
         out, saved = self.ut.forward(x, t, classes.to(torch.int64).contiguous(), rgb_flow, mask, keep)
         warped = flow_warp(out[:, 3:].contiguous(), flow)
-        if df.objective == 'pred_noise':
-            target = noise
-        elif df.objective == 'pred_x0':
-            target = x_start
-        elif df.objective == 'pred_v':
-            ca = df.sqrt_alphas_cumprod.gather(-1, t).contiguous()
-            cb = (-df.sqrt_one_minus_alphas_cumprod).gather(-1, t).contiguous()
-            target = ops.q_sample(noise, x_start, ca, cb)
-        else:
-            raise ValueError(f'unknown objective {df.objective}')
+        target = df._loss_target(x_start, t, noise)
         abar = df.alphas_cumprod.gather(-1, t).to(torch.float32).contiguous()
         loss = ops.loss_combine(ops.diff_mean(out, target, None, squared),
                                 ops.diff_mean(warped, out[:, :3].contiguous(), mask, squared), abar)
@@ -631,13 +617,14 @@ class DDPTrainStep(TrainStep):
 
 
 class _PLoss(torch.autograd.Function):
-    """autograd boundary of GaussianDiffusion.forward: the loss and every parameter gradient are produced together by
-    TrainStep.loss_and_grads (HIP kernels, manual tape); backward() just hands the gradients to autograd."""
+    """autograd boundary of GaussianDiffusion.forward (cfg) / p_losses (ddpm): the loss and every parameter gradient are
+    produced together by ``loss_and_grads()`` (a TrainStep: HIP kernels, manual tape); backward() just hands the gradients to
+    autograd, scaled by the incoming gradient.  ``params``: the parameters, in ``names`` order."""
 
     @staticmethod
-    def forward(ctx, ts, img, classes, *params):
-        loss, grads = ts.loss_and_grads(img, classes)
-        ctx.grads = [grads.get(k) for k in ts.params]
+    def forward(ctx, loss_and_grads, names, *params):
+        loss, grads = loss_and_grads()
+        ctx.grads = [grads.get(k) for k in names]
         return loss.clone()
 
     @staticmethod
@@ -645,7 +632,7 @@ class _PLoss(torch.autograd.Function):
         s = float(gout)
         out = [None if g is None else (g if s == 1.0 else ops.affine(g, s, 0.)) for g in ctx.grads]
         ctx.grads = None
-        return (None, None, None, *out)
+        return (None, None, *out)                            # (nothing for the two non-parameter inputs)
 
 
 def loss_with_grad_fn(diffusion, img, classes):
@@ -653,25 +640,7 @@ def loss_with_grad_fn(diffusion, img, classes):
     if ts is None:
         ts = TrainStep(diffusion)
         diffusion.__dict__['_dmh_train_step'] = ts        # not a submodule / parameter: plain attribute
-    return _PLoss.apply(ts, img, classes, *ts.params.values())
-
-
-class _PLossDDP(torch.autograd.Function):
-    """autograd boundary of ddpm.GaussianDiffusion.p_losses: DDPTrainStep produces the loss and every parameter gradient
-    together; backward() hands the gradients to autograd, scaled by the incoming gradient"""
-
-    @staticmethod
-    def forward(ctx, ts, x_start, t, noise, *params):
-        loss, grads = ts.p_losses_and_grads(x_start, t, noise)
-        ctx.grads = [grads.get(k) for k in ts.params]
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, gout):
-        s = float(gout)
-        out = [None if g is None else (g if s == 1.0 else ops.affine(g, s, 0.)) for g in ctx.grads]
-        ctx.grads = None
-        return (None, None, None, None, *out)
+    return _PLoss.apply(lambda: ts.loss_and_grads(img, classes), list(ts.params), *ts.params.values())
 
 
 def ddp_loss_with_grad_fn(diffusion, x_start, t, noise=None):
@@ -679,4 +648,4 @@ def ddp_loss_with_grad_fn(diffusion, x_start, t, noise=None):
     if not isinstance(ts, DDPTrainStep):
         ts = DDPTrainStep(diffusion)
         diffusion.__dict__['_dmh_train_step'] = ts        # not a submodule / parameter: plain attribute
-    return _PLossDDP.apply(ts, x_start, t, noise, *ts.params.values())
+    return _PLoss.apply(lambda: ts.p_losses_and_grads(x_start, t, noise), list(ts.params), *ts.params.values())

@@ -576,3 +576,95 @@ def test_affine_uint8_qsample(ops):
     nz = rand((2, 6, 5, 5), 4)
     want = ca[:, None, None, None] * x + cb[:, None, None, None] * nz
     assert torch.equal(ops.q_sample(x.to(dev()), nz.to(dev()), ca.to(dev()), cb.to(dev())).cpu(), want)
+
+
+# a DmhStep with no special coefficient (alphas_cumprod = 0.45; no power of two, no 0 / 1): a contraction or a reordering in
+# one kernel moves bits
+_STEP_COEF = dict(sqrt_recip_ac=1.4907119, sqrt_recipm1_ac=1.1055416, sqrt_ac=0.67082042, sqrt_1m_ac=0.74161983,
+                  c0=0.83, c1=0.41, c2=0.37)
+
+
+def _clamp_edge_xt(a):
+    """fp32 (on, outside): fl(a * on) == 1 exactly and fl(a * outside) is the first product above 1 — found by stepping
+    through the neighbours of 1 / a with numpy's correctly rounded fp32 product (the number format alone)"""
+    a = np.float32(a)
+    x = np.float32(1) / a
+    for _ in range(8):
+        x = np.nextafter(x, np.float32(0))
+    on = None
+    for _ in range(64):
+        p = a * x
+        if p == np.float32(1) and on is None:
+            on = x
+        if p > np.float32(1):
+            assert on is not None, f'no fp32 x with fl({a} * x) == 1'
+            return float(on), float(x)
+        x = np.nextafter(x, np.float32(4))
+    raise AssertionError(f'no clamp edge found for coefficient {a}')
+
+
+@pytest.mark.parametrize('H,W', [(4, 5), (3, 5)], ids=['P4', 'P1'])
+def test_sampler_step_wrappers_agree(ops, H, W):
+    """dmh_sampler_step (host DmhStep), dmh_sampler_step_dev (the same struct in device memory) and — without model_null —
+    dmh_sampler_step_ddp_dev are the same step, bit for bit: every objective x mode x clip, cond_scale 3 with a model_null
+    and a keep vector with a dropped row, elements exactly on and just outside both clamp edges, a NaN in model_cond that
+    stays NaN in x_start.  H*W = 20: the fused kernel's 4-pixel path; 15: its 1-pixel path."""
+    from dmhomo_amd._lib import DmhStep
+    B, Cc = 2, 3
+    shape = (B, Cc, H, W)
+    n, per_row = B * Cc * H * W, Cc * H * W
+    d = dev()
+    keep = torch.tensor([0, 1], dtype=torch.uint8, device=d)
+    draws1, draws0 = (torch.tensor([v], dtype=torch.int32, device=d) for v in (1, 0))
+    cursor = torch.zeros((1,), dtype=torch.int32, device=d)
+    p = lambda t: ops.ptr(t)
+    checked = 0
+    for objective in (0, 1, 2):
+        mc, mn, x, noise = (rand(shape, s) * 1.5 for s in (60 + objective, 63, 64, 65))
+        # row 1 (kept), elements 0..3 of channel 0: x_start lands on 1, just above 1, on -1, just below -1
+        if objective == 1:                                   # x0 = null + (cond - null) * 3 = v for cond == null == v
+            on, out = 1., float(np.nextafter(np.float32(1), np.float32(2)))
+            edge = torch.tensor([on, out, -on, -out])
+            mc[1, 0].view(-1)[:4] = edge
+            mn[1, 0].view(-1)[:4] = edge
+        else:                                                # x0 = fl(a * xt) - fl(b * 0) for cond == null == 0
+            on, out = _clamp_edge_xt(_STEP_COEF['sqrt_recip_ac' if objective == 0 else 'sqrt_ac'])
+            mc[1, 0].view(-1)[:4] = 0.
+            mn[1, 0].view(-1)[:4] = 0.
+            x[1, 0].view(-1)[:4] = torch.tensor([on, out, -on, -out])
+        mc[1, 2].view(-1)[7] = float('nan')
+        mc, mn, x, noise = (t.to(d) for t in (mc, mn, x, noise))
+        for mode in (ops.MODE_DDIM, ops.MODE_LAST, ops.MODE_DDPM):
+            nz = None if mode == ops.MODE_LAST else noise
+            for clip in (0, 1):
+                what = (objective, mode, clip)
+                step = DmhStep(objective=objective, clip=clip, mode=mode, cond_scale=3.0, **_STEP_COEF)
+                cur = torch.frombuffer(bytearray(bytes(step)), dtype=torch.uint8).to(d)
+                for null in (mn, None):
+                    kp = keep if null is not None else None
+                    host = ops.sampler_step(step, mc, null, x, nz, True, True, keep=kp)
+                    got = tuple(torch.full(shape, 7., device=d) for _ in range(3))
+                    ops.call('dmh_sampler_step_dev', ops.ptr(cur, torch.uint8), p(mc), p(null), p(x), p(nz), p(got[0]),
+                             p(got[1]), p(got[2]), n, ops.ptr(kp, torch.uint8), per_row)
+                    for name, a, b in zip(('img', 'x_start', 'pred_noise'), host, got):
+                        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (what, null is not None, name)
+                    xs = host[1]
+                    assert torch.isnan(xs[1, 2].view(-1)[7]), what
+                    e = xs[1, 0].view(-1)[:4].cpu()
+                    if clip:
+                        assert e.tolist() == [1., 1., -1., -1.], (what, e)
+                    else:                                    # (the inputs are what they claim to be)
+                        assert e[0] == 1 and e[1] > 1 and e[2] == -1 and e[3] < -1, (what, e)
+                # host is now the step without model_null: the fused kernel on the same struct, in place on a copy of x
+                img, xs = x.clone(), torch.full(shape, 7., device=d)
+                ops.sampler_step_ddp_dev(cur, cursor, draws0 if nz is None else draws1, mc, img, nz, x_start=xs)
+                assert torch.equal(img.view(torch.int32), host[0].view(torch.int32)), what
+                assert torch.equal(xs.view(torch.int32), host[1].view(torch.int32)), what
+                checked += 1
+    assert checked == 3 * 3 * 2
+    # a device entry in mode DDIM without noise (a mis-sequenced cursor; the host entry point refuses it): NaN, no fault
+    step = DmhStep(objective=0, clip=1, mode=ops.MODE_DDIM, cond_scale=3.0, **_STEP_COEF)
+    cur = torch.frombuffer(bytearray(bytes(step)), dtype=torch.uint8).to(d)
+    img = ops.sampler_step_dev(cur, mc, mn, x, None, keep=keep)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(img).all())
