@@ -165,6 +165,9 @@ SIGNATURES = {
     'dmh_preview_sheet': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                   C.c_void_p]),
     'dmh_homography_warp': (c_int, [c_f32p, C.c_void_p, c_f32p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_hem_batch': (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    'dmh_hem_flow': (c_int, [C.c_void_p, c_int, c_int, c_int, c_f32p, C.c_void_p]),
 }
 
 DLT_BLOCKS = 64

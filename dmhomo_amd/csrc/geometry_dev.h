@@ -81,3 +81,16 @@ __device__ __forceinline__ float flow_warp_sample(const float* __restrict__ xc, 
   acc = fmaf(se, t.wse, acc);
   return acc;
 }
+
+// HEM's homo_convert_to_flow (HEM/dataset/data_loader.py:42-52 over from_homography_to_pixel_wise_mapping,
+// flow_and_mapping_operations.py:454-484, and convert_mapping_to_flow, :155-195) for one pixel: the mapping H.(x, y, 1) in
+// float64 with the reference's epsilon 1e-8 on the divisor, rounded to fp32 (map.astype(float32)), minus the fp32 grid.
+// Not G2 (dmh_homography_flow): that one is DDP's get_flow_np with 1e-6 and the subtraction in float64.
+__device__ __forceinline__ void hem_flow_pixel(const double* __restrict__ Hm, int xi, int yi, float& u, float& v) {
+  const double x = (double)xi, y = (double)yi;
+  const double wq = (Hm[6] * x + Hm[7] * y) + Hm[8];
+  const float mx = (float)(((Hm[0] * x + Hm[1] * y) + Hm[2]) / (wq + 1e-8));
+  const float my = (float)(((Hm[3] * x + Hm[4] * y) + Hm[5]) / (wq + 1e-8));
+  u = mx - (float)xi;
+  v = my - (float)yi;
+}

@@ -687,6 +687,38 @@ def homography_warp(src, homos, dsize):
     return dst
 
 
+# ------------------------------------------------------------------ HEM training batches (HEM/dataset/data_loader.py:97-255)
+def hem_batch(img12, homo, homo_inv, start, mean, std, ori_size, crop_size):
+    """DGMTrainData's item arithmetic for a whole batch in one launch: img12 (B,6,h,w) uint8, homo / homo_inv (B,3,3) f64
+    at ``ori_size``, start (B,2) int32 as (x, y) — all on the device; mean / std: three host floats each ->
+    (imgs_gray_full, imgs_rgb_full, flow_gt_full, imgs_gray_patch, flow_gt_patch)."""
+    B, six, h, w = img12.shape
+    (H, W), (ph, pw) = ori_size, crop_size
+    assert six == 6 and homo.shape == (B, 3, 3) and homo_inv.shape == (B, 3, 3) and start.shape == (B, 2), \
+        (img12.shape, homo.shape, homo_inv.shape, start.shape)
+    m3, s3 = (C.c_double * 3)(*[float(v) for v in mean]), (C.c_double * 3)(*[float(v) for v in std])
+    pin, dev = ptr(img12, torch.uint8), img12.device          # (refuses a CPU tensor before anything is allocated)
+    gray = torch.empty((B, 2, H, W), device=dev, dtype=F32)
+    rgb = torch.empty((B, 6, H, W), device=dev, dtype=F32)
+    flow = torch.empty((B, 4, H, W), device=dev, dtype=F32)
+    gray_p = torch.empty((B, 2, ph, pw), device=dev, dtype=F32)
+    flow_p = torch.empty((B, 4, ph, pw), device=dev, dtype=F32)
+    call('dmh_hem_batch', pin, ptr(homo, torch.float64), ptr(homo_inv, torch.float64), ptr(start, torch.int32),
+         C.cast(m3, C.c_void_p), C.cast(s3, C.c_void_p), B, h, w, int(H), int(W), int(ph), int(pw), ptr(gray), ptr(rgb),
+         ptr(flow), ptr(gray_p), ptr(flow_p))
+    return gray, rgb, flow, gray_p, flow_p
+
+
+def hem_flow(homo, H, W):
+    """homo_convert_to_flow (data_loader.py:42-52): homo (B,3,3) f64 device -> flow (B,2,H,W) fp32."""
+    B = homo.shape[0]
+    assert homo.shape == (B, 3, 3), homo.shape
+    ph = ptr(homo, torch.float64)
+    flow = torch.empty((B, 2, int(H), int(W)), device=homo.device, dtype=F32)
+    call('dmh_hem_flow', ph, B, int(H), int(W), ptr(flow))
+    return flow
+
+
 # ------------------------------------------------------------------ training (SURVEY 8f row 1, first pieces)
 def conv_wgrad(dy, src0, src1=None, k=3, in_coef=None, want_bias=True, ups=0):
     """weight (and bias) gradient of the stride-1 kxk conv whose input was cat(src0, src1) (after the optional

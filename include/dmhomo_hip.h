@@ -527,6 +527,28 @@ int dmh_preview_sheet(const float* img, const float* mask, const float* flow, un
  * fixed-point coefficient tables (fraction quantised to 1/32). */
 int dmh_homography_warp(const float* src, const double* homos, float* dst, int B, int H, int W, int Hd, int Wd, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * HEM training batches from sampled pairs: DGMTrainData.__getitem__ / data_aug, HEM/dataset/data_loader.py:121-255,
+ * a batch per launch (dmhomo_amd/hem_data.py)
+ * ------------------------------------------------------------------------------------- */
+/* img12 uint8 [B][6][h][w] (a saveTrainPair record, channel-planar); homo, homo_inv f64 [B][9] (device): the forward
+ * homography at the output size and its inverse; start int32 [B][2] (device): the crop's (x, y); mean, std: HOST f64 [3].
+ * (h, w) != (H, W): both images are resized with cv2's 8-bit INTER_LINEAR arithmetic (integer, bit-exact), else taken as is.
+ * Outputs fp32, as the reference's collated batch:
+ *   imgs_gray_full [B][2][H][W]  channel mean of (u8 - mean) / std in float64
+ *   imgs_rgb_full  [B][6][H][W]  u8 / 255
+ *   flow_gt_full   [B][4][H][W]  planes 0-1 dmh_hem_flow of homo_inv, planes 2-3 of homo
+ *   imgs_gray_patch [B][2][ph][pw], flow_gt_patch [B][4][ph][pw]: bit for bit the window [y:y+ph, x:x+pw] of the full tensors.
+ * A start outside [0, W-pw] x [0, H-ph] is device data: that sample's patch tensors are filled with NaN, nothing is read or
+ * written out of bounds.  The full-size outputs must be 16-byte aligned. */
+int dmh_hem_batch(const unsigned char* img12, const double* homo, const double* homo_inv, const int32_t* start,
+                  const double* mean, const double* std, int B, int h, int w, int H, int W, int ph, int pw,
+                  float* imgs_gray_full, float* imgs_rgb_full, float* flow_gt_full, float* imgs_gray_patch,
+                  float* flow_gt_patch, void* stream);
+/* homo_convert_to_flow (data_loader.py:42-52) alone: homo f64 [B][9] (device) -> flow fp32 [B][2][H][W] (16-byte aligned),
+ * flow = fp32(H.(x, y, 1) / (w' + 1e-8)) - fp32(x, y), the mapping in float64 */
+int dmh_hem_flow(const double* homo, int B, int H, int W, float* flow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
