@@ -143,6 +143,12 @@ SIGNATURES = {
                                  C.c_void_p]),
     'dmh_sampler_step_ddp_dev': (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p,
                                          c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_sampler_step_ms': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, C.c_void_p,
+                                    c_i64, C.c_void_p]),
+    'dmh_sampler_step_ms_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, C.c_void_p, c_i64,
+                                        C.c_void_p]),
+    'dmh_sampler_step_ddp_ms_dev': (c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int,
+                                            c_int, c_int, C.c_void_p]),
     'dmh_rng_indexed': (c_int, [c_f32p, c_int, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     'dmh_rng_keep_mask': (c_int, [C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_float, C.c_void_p]),
     'dmh_rows_lincomb': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, C.c_void_p]),

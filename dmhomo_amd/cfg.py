@@ -267,6 +267,23 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
+    def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
+        """the loop of _ddim_sample with the multistep solver's update (ScheduleHost._dpmpp_steps; not in the reference): the
+        network call — its class-dropout draw included — is the same, the update draws nothing and carries the previous step's
+        x_start in ``hist``.  ``trace`` as _ddim_sample."""
+        batch, device = shape[0], self.betas.device
+        steps = self._dpmpp_steps(clip_denoised, cond_scale)
+        img = self.rng.randn(shape, device).contiguous()
+        hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
+        for time, step, _ in steps:
+            time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
+            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
+            img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
+            if trace is not None:
+                trace.append({'time': time, 'x_start': x_start, 'img': img})
+        img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
+        return img, mask, flow
+
     @torch.no_grad()
     def p_sample_loop(self, classes, shape, cond_scale=3.):
         # CFG:656 takes (classes, shape, cond_scale) while CFG:719-720 calls it with six arguments, and
@@ -281,27 +298,33 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         """CFG:713-720."""
         batch_size, image_size, channels = classes.shape[0], self.image_size, self.channels
         shape = (batch_size, channels, image_size, image_size)
-        if not self.is_ddim_sampling:
+        solver = self._check_sampler() == 'dpmpp_2m'         # (walks the time list whatever is_ddim_sampling says)
+        if not self.is_ddim_sampling and not solver:
             return self.p_sample_loop(classes, rgb_flow, flow, mask, shape, cond_scale)    # TypeError, as CFG:719-720
         if self.hip_graph and type(self.rng) is DeviceRng and self.sampling_timesteps >= 1:
             return self._sample_graphed(classes, rgb_flow, flow, mask, shape, cond_scale)
         rgb_flow = ops.affine(rgb_flow.to(torch.float32), 2., -1.)      # normalize_to_neg_one_to_one, CFG:716
+        if solver:
+            return self._dpmpp_sample(classes, rgb_flow, flow, mask, shape, cond_scale)
         return self.ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale)
 
     def _graph_tables(self, cond_scale, clip=True):
         """host side of the replayed loop: (steps, times, draws), entry k = the DmhStep, timestep and 'draws noise' flag
-        _ddim_sample passes at its k-th step."""
-        times, steps, draws = map(list, zip(*self._ddim_steps(clip, cond_scale)))
+        _ddim_sample (or, with sampler = 'dpmpp_2m', _dpmpp_sample) passes at its k-th step."""
+        times, steps, draws = map(list, zip(*self._sampler_steps(clip, cond_scale)))
         return steps, times, draws
 
     def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale):
-        """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times"""
+        """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times.
+        With sampler = 'dpmpp_2m' the step is the network, dmh_sampler_step_ms_dev on a static history buffer and the seek:
+        no randn launch is left in it."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
+        solver = self._check_sampler() == 'dpmpp_2m'
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
                bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
-               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key())
+               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key(), self.sampler)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -311,15 +334,24 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             T_tab, C_tab = eng.ss_tables(times)
             st['ss_tab'] = (T_tab, C_tab, st['cursor'])
 
+            if solver:
+                st['hist'] = torch.zeros(shape, device=device)
+
             def mid():                                       # one denoise step of CFG:684-707, in place on st['img']
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
-                noise = self.rng.randn(shape, device).contiguous()
-                ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=st['img'], keep=computed)
+                if solver:
+                    ops.sampler_step_ms_dev(st['cur'], cond, null, st['img'], st['hist'], out=st['img'], keep=computed)
+                else:
+                    noise = self.rng.randn(shape, device).contiguous()
+                    ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=st['img'], keep=computed)
                 ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
 
             def last():                                      # CFG:693-695 + unnormalize, CFG:709
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
-                x0 = ops.sampler_step_dev(st['cur'], cond, null, st['img'], None, keep=computed)
+                if solver:
+                    x0 = ops.sampler_step_ms_dev(st['cur'], cond, null, st['img'], st['hist'], keep=computed)
+                else:
+                    x0 = ops.sampler_step_dev(st['cur'], cond, null, st['img'], None, keep=computed)
                 return ops.affine(x0, 0.5, 0.5)
             return mid, last
 

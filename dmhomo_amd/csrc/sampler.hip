@@ -145,9 +145,10 @@ __device__ __forceinline__ float guided_logit(const float* mc, const float* mn, 
 
 // ONE denoise step on one element, the only statement of it: every step kernel below calls this, so the eager, the captured
 // and the fused path cannot differ in a bit.  mo: guided_logit, xt: the current image, nz: the entry's noise value, has_noise:
-// whether the DDPM update adds it (a DDIM update always does) -> x0 (x_start), pn (pred_noise), o (the next image)
-__device__ __forceinline__ void denoise_step(const DmhStep& s, float mo, float xt, float nz, bool has_noise, float& x0,
-                                             float& pn, float& o) {
+// whether the DDPM update adds it (a DDIM update always does), prev: the previous step's x0 (read by a multistep entry with
+// c2 != 0 only) -> x0 (x_start), pn (pred_noise), o (the next image)
+__device__ __forceinline__ void denoise_step(const DmhStep& s, float mo, float xt, float nz, bool has_noise, float prev,
+                                             float& x0, float& pn, float& o) {
   if (s.objective == 0) {  // pred_noise, CFG:614-617
     pn = mo;
     x0 = s.sqrt_recip_ac * xt - s.sqrt_recipm1_ac * pn;
@@ -165,24 +166,36 @@ __device__ __forceinline__ void denoise_step(const DmhStep& s, float mo, float x
     o = x0 * s.c0 + s.c1 * pn + s.c2 * nz;
   } else if (s.mode == 1) {  // last DDIM step, CFG:693-695
     o = x0;
-  } else {  // DDPM posterior step, DDP:604-611,660: mean + exp(.5 logvar) * noise (no noise at t == 0)
+  } else if (s.mode == 2) {  // DDPM posterior step, DDP:604-611,660: mean + exp(.5 logvar) * noise (no noise at t == 0)
     o = s.c0 * x0 + s.c1 * xt;
     if (has_noise) o = o + s.c2 * nz;
+  } else {  // multistep (DPM-Solver++ 2M, data prediction): c2 == 0 is its first-order update and leaves prev unread
+    o = s.c0 * x0 + s.c1 * xt;
+    if (s.c2 != 0.f) o = o + s.c2 * prev;
   }
 }
 
-// the body of the two element-per-thread step kernels.  missing: what stands for the noise of an entry that has none
+// whether an entry reads the x0 history of the multistep solver
+__device__ __forceinline__ bool reads_history(const DmhStep& s) { return s.mode == 3 && s.c2 != 0.f; }
+
+// the body of the element-per-thread step kernels.  missing: what stands for the noise of an entry that has none, and for the
+// history of a multistep entry that reads one without hist.  hist (the multistep kernels): [n], the previous step's x0 — a
+// thread reads its own element where the entry needs it, then stores the new x0 there
 __device__ __forceinline__ void sampler_step_body(const DmhStep& s, const float* mc, const float* mn, const float* x,
-                                                  const float* noise, float* img_out, float* x_start, float* pred_noise,
-                                                  int64_t n, const uint8_t* keep, int64_t per_row, float missing) {
+                                                  const float* noise, float* hist, float* img_out, float* x_start,
+                                                  float* pred_noise, int64_t n, const uint8_t* keep, int64_t per_row,
+                                                  float missing) {
+  const bool history = hist && reads_history(s);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float mo = guided_logit(mc, mn, keep, i, per_row, s.cond_scale);
     const float nz = (noise && s.mode != 1) ? noise[i] : missing;
+    const float prev = history ? hist[i] : missing;
     float x0, pn, o;
-    denoise_step(s, mo, x[i], nz, noise != nullptr, x0, pn, o);
+    denoise_step(s, mo, x[i], nz, noise != nullptr, prev, x0, pn, o);
     img_out[i] = o;
     if (x_start) x_start[i] = x0;
     if (pred_noise) pred_noise[i] = pn;
+    if (hist) hist[i] = x0;
   }
 }
 
@@ -192,7 +205,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(DmhStep s, const floa
                                                            const float* __restrict__ noise, float* __restrict__ img_out,
                                                            float* __restrict__ x_start, float* __restrict__ pred_noise,
                                                            int64_t n, const uint8_t* __restrict__ keep, int64_t per_row) {
-  sampler_step_body(s, mc, mn, x, noise, img_out, x_start, pred_noise, n, keep, per_row, 0.f);
+  sampler_step_body(s, mc, mn, x, noise, nullptr, img_out, x_start, pred_noise, n, keep, per_row, 0.f);
 }
 
 // the step kernel with its DmhStep read from device memory (dmh_sampler_step_dev); no __restrict__ on x / img_out: the
@@ -205,7 +218,24 @@ __global__ __launch_bounds__(256) void sampler_step_dev_kernel(const DmhStep* __
                                                                float* __restrict__ x_start, float* __restrict__ pred_noise,
                                                                int64_t n, const uint8_t* __restrict__ keep, int64_t per_row) {
   const DmhStep s = *sp;
-  sampler_step_body(s, mc, mn, x, noise, img_out, x_start, pred_noise, n, keep, per_row, __builtin_nanf(""));
+  sampler_step_body(s, mc, mn, x, noise, nullptr, img_out, x_start, pred_noise, n, keep, per_row, __builtin_nanf(""));
+}
+
+// the multistep step (dmh_sampler_step_ms / _ms_dev): no noise, the x0 history instead.  No __restrict__ on x / img_out (in
+// place, as above) nor on hist (read, then written, by the same thread)
+__global__ __launch_bounds__(256) void sampler_step_ms_kernel(DmhStep s, const float* __restrict__ mc,
+                                                              const float* __restrict__ mn, const float* x, float* hist,
+                                                              float* img_out, float* __restrict__ x_start, int64_t n,
+                                                              const uint8_t* __restrict__ keep, int64_t per_row) {
+  sampler_step_body(s, mc, mn, x, nullptr, hist, img_out, x_start, nullptr, n, keep, per_row, __builtin_nanf(""));
+}
+
+__global__ __launch_bounds__(256) void sampler_step_ms_dev_kernel(const DmhStep* __restrict__ sp, const float* __restrict__ mc,
+                                                                  const float* __restrict__ mn, const float* x, float* hist,
+                                                                  float* img_out, float* __restrict__ x_start, int64_t n,
+                                                                  const uint8_t* __restrict__ keep, int64_t per_row) {
+  const DmhStep s = *sp;
+  sampler_step_body(s, mc, mn, x, nullptr, hist, img_out, x_start, nullptr, n, keep, per_row, __builtin_nanf(""));
 }
 
 // dmh_sampler_step_ddp_dev: the replayed step of the unconditional loop (DDP:647-729) in one pass — denoise_step on the entry
@@ -214,16 +244,20 @@ __global__ __launch_bounds__(256) void sampler_step_dev_kernel(const DmhStep* __
 // input written as dmh_assemble_input writes it.  One thread per P pixels of a row and every channel: P = 4 when HW % 4 == 0,
 // where the 4 pixels of one channel are exactly one Philox counter quad; P = 1 otherwise (a thread then draws its element's
 // quad and keeps one lane).  The channel loop is not unrolled and no array is indexed by a runtime value (no scratch).
-template <int P>
+// MS (dmh_sampler_step_ddp_ms_dev): the multistep solver's step — no noise source, no draws table, no generator ticket; hist
+// [B][C][HW] holds the previous step's x0, read where the entry needs it and overwritten with this step's by the same thread.
+template <int P, bool MS>
 __global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __restrict__ sp, const int32_t* __restrict__ cursor,
                                                                const int32_t* __restrict__ draws, const float* __restrict__ mc,
                                                                float* img, const float* __restrict__ noise,
                                                                const int64_t* __restrict__ ids, unsigned long long* state,
-                                                               float* __restrict__ x_start, float* __restrict__ xin, int C, int HW,
-                                                               int cpad, int sc, int64_t ngroups) {
+                                                               float* hist, float* __restrict__ x_start,
+                                                               float* __restrict__ xin, int C, int HW, int cpad, int sc,
+                                                               int64_t ngroups) {
   const DmhStep s = *sp;
-  const bool drawn = draws[*cursor] != 0;   // eager runs this entry with noise (else: no draw, no advance)
-  const bool keyed = ids != nullptr && drawn;
+  const bool drawn = MS ? false : draws[*cursor] != 0;   // eager runs this entry with noise (else: no draw, no advance)
+  const bool keyed = !MS && ids != nullptr && drawn;
+  const bool history = MS && reads_history(s);
   unsigned long long seed = 0, draw = 0;
   if (keyed) seed = state[0], draw = state[1];
   const int G = HW / P;
@@ -235,7 +269,7 @@ __global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __
     float* xo = xin ? xin + ((size_t)b * HW + p0) * cpad : nullptr;
     for (int c = 0; c < C; ++c) {
       const size_t base = ((size_t)b * C + c) * HW + p0;
-      float mo[P], xt[P], nz[P];
+      float mo[P], xt[P], nz[P], pv[P];
       if constexpr (P == 4) {
         const float4 m4 = ld4(mc + base), x4 = ld4(img + base);
         mo[0] = m4.x, mo[1] = m4.y, mo[2] = m4.z, mo[3] = m4.w;
@@ -243,6 +277,16 @@ __global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __
       } else {
         mo[0] = mc[base];
         xt[0] = img[base];
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) pv[j] = __builtin_nanf("");
+      if (history) {
+        if constexpr (P == 4) {
+          const float4 h4 = ld4(hist + base);
+          pv[0] = h4.x, pv[1] = h4.y, pv[2] = h4.z, pv[3] = h4.w;
+        } else {
+          pv[0] = hist[base];
+        }
       }
       if (keyed) {
         const int64_t e = (int64_t)c * HW + p0;   // element of the row: counter quad e / 4, lane e % 4
@@ -269,9 +313,10 @@ __global__ __launch_bounds__(256) void sampler_step_ddp_kernel(const DmhStep* __
 #pragma unroll
       for (int j = 0; j < P; ++j) {
         float x0, pn, o;
-        denoise_step(s, mo[j], xt[j], nz[j], drawn, x0, pn, o);
+        denoise_step(s, mo[j], xt[j], nz[j], drawn, pv[j], x0, pn, o);
         img[base + j] = o;
         if (x_start) x_start[base + j] = x0;
+        if constexpr (MS) hist[base + j] = x0;
         if (xo) {   // cat((x_start, img)) with self-conditioning, img alone without (DDP:411), NHWC
           if (sc) {
             xo[(size_t)j * cpad + c] = x0;
@@ -500,12 +545,65 @@ extern "C" int dmh_sampler_step_ddp_dev(const DmhStep* cur_dev, const int32_t* c
   grid = grid < 1024 ? grid : 1024;
   hipStream_t st = (hipStream_t)stream;
   if (quad)
-    hipLaunchKernelGGL(sampler_step_ddp_kernel<4>, dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img, noise,
-                       sample_ids, (unsigned long long*)state, x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+    hipLaunchKernelGGL((sampler_step_ddp_kernel<4, false>), dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img,
+                       noise, sample_ids, (unsigned long long*)state, (float*)nullptr, x_start, xin_next, C, HW, cpad, self_cond,
+                       ngroups);
   else
-    hipLaunchKernelGGL(sampler_step_ddp_kernel<1>, dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img, noise,
-                       sample_ids, (unsigned long long*)state, x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+    hipLaunchKernelGGL((sampler_step_ddp_kernel<1, false>), dim3(grid), dim3(256), 0, st, cur_dev, cursor, draws, model_out, img,
+                       noise, sample_ids, (unsigned long long*)state, (float*)nullptr, x_start, xin_next, C, HW, cpad, self_cond,
+                       ngroups);
   DMH_CHECK_LAUNCH("dmh_sampler_step_ddp_dev");
+  return DMH_OK;
+}
+
+extern "C" int dmh_sampler_step_ms(const DmhStep* s, const float* model_cond, const float* model_null, const float* x,
+                                   float* hist, float* img_out, float* x_start, int64_t n, const uint8_t* keep,
+                                   int64_t per_row, void* stream) {
+  DMH_REQUIRE(s && model_cond && x && hist && img_out && n > 0, "dmh_sampler_step_ms: bad arguments");
+  DMH_REQUIRE(!keep || (model_null && per_row > 0 && n % per_row == 0), "dmh_sampler_step_ms: keep needs model_null and per_row dividing n");
+  DMH_REQUIRE(s->objective >= 0 && s->objective <= 2 && (s->mode == 1 || s->mode == 3),
+              "dmh_sampler_step_ms: bad enum (mode: 1 last step or 3 multistep)");
+  hipLaunchKernelGGL(sampler_step_ms_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, *s, model_cond, model_null,
+                     x, hist, img_out, x_start, n, keep, per_row);
+  DMH_CHECK_LAUNCH("dmh_sampler_step_ms");
+  return DMH_OK;
+}
+
+extern "C" int dmh_sampler_step_ms_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null,
+                                       const float* x, float* hist, float* img_out, float* x_start, int64_t n,
+                                       const uint8_t* keep, int64_t per_row, void* stream) {
+  DMH_REQUIRE(cur_dev && model_cond && x && hist && img_out && n > 0, "dmh_sampler_step_ms_dev: bad arguments");
+  DMH_REQUIRE(!keep || (model_null && per_row > 0 && n % per_row == 0), "dmh_sampler_step_ms_dev: keep needs model_null and per_row dividing n");
+  hipLaunchKernelGGL(sampler_step_ms_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, cur_dev, model_cond,
+                     model_null, x, hist, img_out, x_start, n, keep, per_row);
+  DMH_CHECK_LAUNCH("dmh_sampler_step_ms_dev");
+  return DMH_OK;
+}
+
+extern "C" int dmh_sampler_step_ddp_ms_dev(const DmhStep* cur_dev, const int32_t* cursor, const float* model_out, float* img,
+                                           float* hist, float* x_start, float* xin_next, int B, int C, int HW, int cpad,
+                                           int self_cond, void* stream) {
+  DMH_REQUIRE(cur_dev && cursor && model_out && img && hist && B > 0 && C > 0 && HW > 0 && (self_cond == 0 || self_cond == 1),
+              "dmh_sampler_step_ddp_ms_dev: bad arguments");
+  const int cin = self_cond ? 2 * C : C;
+  DMH_REQUIRE(C <= 4096 && cpad % 4 == 0 && cpad >= cin && cpad <= 16384,
+              "dmh_sampler_step_ddp_ms_dev: cpad=%d must be a multiple of 4 >= %d input channels", cpad, cin);
+  DMH_REQUIRE((int64_t)B * HW < ((int64_t)1 << 31) && (int64_t)C * HW < ((int64_t)1 << 34),
+              "dmh_sampler_step_ddp_ms_dev: B=%d x HW=%d pixels (limit 2^31), C=%d x HW elements per row (limit 2^34)", B, HW, C);
+  const bool quad = HW % 4 == 0 &&
+                    (((uintptr_t)model_out | (uintptr_t)img | (uintptr_t)hist | (uintptr_t)x_start) & 15) == 0;
+  const int64_t ngroups = (int64_t)B * HW / (quad ? 4 : 1);
+  const unsigned grid = grid_for(ngroups);
+  hipStream_t st = (hipStream_t)stream;
+  if (quad)
+    hipLaunchKernelGGL((sampler_step_ddp_kernel<4, true>), dim3(grid), dim3(256), 0, st, cur_dev, cursor, (const int32_t*)nullptr,
+                       model_out, img, (const float*)nullptr, (const int64_t*)nullptr, (unsigned long long*)nullptr, hist,
+                       x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+  else
+    hipLaunchKernelGGL((sampler_step_ddp_kernel<1, true>), dim3(grid), dim3(256), 0, st, cur_dev, cursor, (const int32_t*)nullptr,
+                       model_out, img, (const float*)nullptr, (const int64_t*)nullptr, (unsigned long long*)nullptr, hist,
+                       x_start, xin_next, C, HW, cpad, self_cond, ngroups);
+  DMH_CHECK_LAUNCH("dmh_sampler_step_ddp_ms_dev");
   return DMH_OK;
 }
 

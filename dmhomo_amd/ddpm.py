@@ -142,6 +142,26 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         ops.affine_tail_(img, img.shape[1] - 2, 2. * 512, -512.)   # (x*2-1)*512, DDP:728
         return img
 
+    @torch.no_grad()
+    def dpmpp_sample(self, shape, clip_denoised=True):
+        """ddim_sample's loop and output mapping (DDP:727-728) with the multistep solver's update (ScheduleHost._dpmpp_steps;
+        not in the reference): no noise after the first draw; ``hist`` carries the previous step's x_start."""
+        if self._graphed():
+            return self._sample_graphed(shape, 'dpmpp_2m', bool(clip_denoised))
+        batch, device = shape[0], self.betas.device
+        steps = self._dpmpp_steps(clip_denoised)
+        img = self.rng.randn(shape, device).contiguous()
+        hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
+        x_start = None
+        for time, step, _ in steps:
+            time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
+            self_cond = x_start if self.self_condition else None
+            out = self.model(img, time_cond, self_cond)
+            img, x_start = ops.sampler_step_ms(step, out, None, img, hist, want_x_start=True)
+        img = ops.affine(img, 0.5, 0.5)
+        ops.affine_tail_(img, img.shape[1] - 2, 2. * 512, -512.)   # as ddim_sample, DDP:728
+        return img
+
     def _graphed(self):
         return bool(self.hip_graph) and type(self.rng) is DeviceRng and self.betas.is_cuda
 
@@ -154,6 +174,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                        for t in reversed(range(0, self.num_timesteps))]
         elif kind == 'ddim':
             entries = self._ddim_steps(clip)
+        elif kind == 'dpmpp_2m':
+            entries = self._dpmpp_steps(clip)
         else:
             raise ValueError(f'unknown sampling loop {kind!r}')
         times, steps, draws = map(list, zip(*entries))
@@ -180,6 +202,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             keyed = rng.keyed
             ids = rng.ids_for(B) if keyed else None
             scale, shift = (2., -1.) if kind == 'ddpm' else (2. * 512, -512.)     # DDP:679 / DDP:728
+            solver = kind == 'dpmpp_2m'
+            if solver:
+                st['hist'] = torch.zeros(shape, device=device)
 
             def network():                                   # Unet.forward on the static input (DDP:400-447)
                 cond = eng.embed(st['tcond'], None, 1)
@@ -187,6 +212,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
             def mid():                                       # one step of DDP:663-680 / 700-726, in place on st['img']
                 out = network()
+                if solver:                                   # (no noise: nothing is drawn inside the step)
+                    ops.sampler_step_ddp_ms_dev(st['cur'], st['cursor'], out, st['img'], st['hist'], xin=st['xin'], self_cond=sc)
+                    ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
+                    return
                 noise = None if keyed else rng.randn(shape, device)     # (torch's generator: its offsets are graph inputs)
                 ops.sampler_step_ddp_dev(st['cur'], st['cursor'], st['draws'], out, st['img'], noise, ids,
                                          rng.state if keyed else None, xin=st['xin'], self_cond=sc)
@@ -194,7 +223,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
             def last():                                      # the last step (no noise) + unnormalise, DDP:678-679 / 727-728
                 out = network()
-                ops.sampler_step_ddp_dev(st['cur'], st['cursor'], st['draws'], out, st['img'])
+                if solver:
+                    ops.sampler_step_ddp_ms_dev(st['cur'], st['cursor'], out, st['img'], st['hist'])
+                else:
+                    ops.sampler_step_ddp_dev(st['cur'], st['cursor'], st['draws'], out, st['img'])
                 img = ops.affine(st['img'], 0.5, 0.5)
                 ops.affine_tail_(img, Cc - 2, scale, shift)
                 return img
@@ -210,6 +242,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def sample(self, batch_size=16):
         """DDP:731-735."""
         shape = (batch_size, self.channels, self.image_size, self.image_size)
+        if self._check_sampler() == 'dpmpp_2m':              # (walks the time list whatever is_ddim_sampling says)
+            return self.dpmpp_sample(shape)
         return self.ddim_sample(shape) if self.is_ddim_sampling else self.p_sample_loop(shape)
 
     @torch.no_grad()

@@ -400,7 +400,7 @@ def final_conv_nchw(x, w, bias):
 
 
 OBJECTIVE = {'pred_noise': 0, 'pred_x0': 1, 'pred_v': 2}
-MODE_DDIM, MODE_LAST, MODE_DDPM = 0, 1, 2
+MODE_DDIM, MODE_LAST, MODE_DDPM, MODE_MULTISTEP = 0, 1, 2, 3
 
 
 def sampler_step(step, model_cond, model_null, x, noise, want_x_start=True, want_pred_noise=False, keep=None):
@@ -422,7 +422,7 @@ def step_table(steps, times, device):
     if n < 1 or len(times) != n:
         raise ValueError(f'step_table: {n} steps, {len(times)} times')
     for i, st in enumerate(steps):
-        if st.objective not in (0, 1, 2) or st.mode not in (MODE_DDIM, MODE_LAST, MODE_DDPM):
+        if st.objective not in (0, 1, 2) or st.mode not in (MODE_DDIM, MODE_LAST, MODE_DDPM, MODE_MULTISTEP):
             raise ValueError(f'step_table: entry {i} has objective {st.objective} / mode {st.mode}')
         if (st.mode == MODE_LAST) != (i == n - 1) and st.mode != MODE_DDPM:
             raise ValueError(f'step_table: entry {i} of {n} has mode {st.mode}: MODE_LAST belongs to the last entry only')
@@ -472,6 +472,49 @@ def sampler_step_ddp_dev(cur, cursor, draws, model_out, img, noise=None, sample_
     call('dmh_sampler_step_ddp_dev', ptr(cur, torch.uint8), ptr(cursor, torch.int32), ptr(draws, torch.int32), ptr(model_out),
          ptr(img), ptr(noise), ptr(sample_ids, torch.int64), ptr(state, torch.int64), ptr(x_start), ptr(xin), B, Cc, H * W, cpad,
          int(bool(self_cond)))
+    return img
+
+
+def sampler_step_ms(step, model_cond, model_null, x, hist, out=None, want_x_start=False, keep=None):
+    """one step of the multistep solver (dmh_sampler_step_ms): MODE_MULTISTEP or MODE_LAST, no noise; ``hist`` (x's shape) is
+    the previous step's x_start, read when the entry's c2 != 0 and overwritten with this step's.  out may be x (in place).
+    -> (img, x_start or None)"""
+    if tuple(hist.shape) != tuple(x.shape):
+        raise ValueError(f'sampler_step_ms: hist {tuple(hist.shape)} against x {tuple(x.shape)}')
+    img = torch.empty_like(x) if out is None else out
+    xs = torch.empty_like(x) if want_x_start else None
+    call('dmh_sampler_step_ms', C.byref(step), ptr(model_cond), ptr(model_null), ptr(x), ptr(hist), ptr(img), ptr(xs),
+         x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img, xs
+
+
+def sampler_step_ms_dev(cur, model_cond, model_null, x, hist, out=None, x_start=None, keep=None):
+    """sampler_step_ms with its DmhStep in device memory (``cur`` of step_table); out may be x (in place)."""
+    if tuple(hist.shape) != tuple(x.shape):
+        raise ValueError(f'sampler_step_ms_dev: hist {tuple(hist.shape)} against x {tuple(x.shape)}')
+    img = torch.empty_like(x) if out is None else out
+    call('dmh_sampler_step_ms_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(hist), ptr(img),
+         ptr(x_start), x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img
+
+
+def sampler_step_ddp_ms_dev(cur, cursor, model_out, img, hist, x_start=None, xin=None, self_cond=False):
+    """the multistep solver's replayed step of the unconditional loop in one launch (dmh_sampler_step_ddp_ms_dev), in place on
+    img (B,C,H,W): entry ``cur`` of step_table, ``hist`` as sampler_step_ms, x_start and the next step's network input ``xin``
+    as sampler_step_ddp_dev."""
+    B, Cc, H, W = img.shape
+    for t in (model_out, hist, x_start):
+        if t is not None and tuple(t.shape) != (B, Cc, H, W):
+            raise ValueError(f'sampler_step_ddp_ms_dev: {tuple(t.shape)} against img {(B, Cc, H, W)}')
+    cin = Cc * (2 if self_cond else 1)
+    if xin is not None:
+        if xin.dim() != 4 or tuple(xin.shape[:3]) != (B, H, W):
+            raise ValueError(f'sampler_step_ddp_ms_dev: xin {tuple(xin.shape)} against img {(B, Cc, H, W)}')
+        cpad = xin.shape[3]
+    else:
+        cpad = (cin + 3) // 4 * 4
+    call('dmh_sampler_step_ddp_ms_dev', ptr(cur, torch.uint8), ptr(cursor, torch.int32), ptr(model_out), ptr(img), ptr(hist),
+         ptr(x_start), ptr(xin), B, Cc, H * W, cpad, int(bool(self_cond)))
     return img
 
 

@@ -2,6 +2,7 @@
 reference's small helpers, the device noise source, the host mirrors of the schedule with the per-step ``DmhStep``
 records built from them, and the captured-and-replayed sampling loop (``hip_graph``)."""
 from collections import OrderedDict, namedtuple
+import math
 
 import torch
 
@@ -276,6 +277,58 @@ class ScheduleHost:
                 steps.append((time, self._step(host, time, ops.MODE_DDIM, clip, self._ddim_coef(host, time, time_next),
                                                cond_scale), 1))
         return steps
+
+    # OPT-IN, 'ddim' by default (every existing result stays what it is).  'dpmpp_2m': sample() of both classes runs the
+    # second-order multistep solver DPM-Solver++ 2M in data prediction (Lu et al. 2022; the reference has no such solver) over
+    # the same ``sampling_timesteps`` time list as DDIM, whatever is_ddim_sampling says.  Deterministic: no per-step noise, and
+    # ``ddim_sampling_eta`` is ignored.  On an analytic Gaussian model its discretisation error at 16 steps is below DDIM's
+    # (eta = 0) at 32 (tests/test_solver_host.py); what it does to samples of trained weights has not been measured.
+    sampler = 'ddim'
+    SAMPLERS = ('ddim', 'dpmpp_2m')
+
+    def _check_sampler(self):
+        if self.sampler not in self.SAMPLERS:
+            raise ValueError(f'unknown sampler {self.sampler!r}: one of {self.SAMPLERS}')
+        return self.sampler
+
+    def _dpmpp_steps(self, clip, cond_scale=1.):
+        """the DPM-Solver++ 2M loop as a list of (time, DmhStep, 0), over the time pairs of _ddim_steps.  With a_k =
+        sqrt(abar[t_k]), s_k = sqrt(1 - abar[t_k]), lam_k = ln(a_k / s_k), h_k = lam_{k+1} - lam_k and e_k = -expm1(-h_k), entry
+        k moves to t_{k+1} by  img' = c1 * img + c0 * x0_k + c2 * x0_{k-1}  (x0: the clamped data prediction, as DDIM's):
+        c1 = s_{k+1} / s_k; first order (entry 0, and the last entry that updates: 'lower order final') c0 = a_{k+1} e_k,
+        c2 = 0; second order, r = h_{k-1} / h_k: c0 = a_{k+1} e_k (1 + 1/(2r)), c2 = -a_{k+1} e_k / (2r).  float64 from the
+        fp32 alphas_cumprod buffer.  The entry with time_next < 0 returns x0 (MODE_LAST)."""
+        host = self._host()
+        abar = host['alphas_cumprod'].double()
+        pairs = ddim_pairs(self.num_timesteps, self.sampling_timesteps)
+        if any(tn >= t for t, tn in pairs):
+            raise ValueError(f'dpmpp_2m: the sampling times {[t for t, _ in pairs]} are not strictly decreasing '
+                             f'(sampling_timesteps = {self.sampling_timesteps} of {self.num_timesteps}): a step of width 0')
+
+        def a_s_lam(t):
+            a, sg = math.sqrt(float(abar[t])), math.sqrt(1. - float(abar[t]))
+            return a, sg, math.log(a / sg)
+        updating = [k for k, (_, tn) in enumerate(pairs) if tn >= 0]
+        steps, h_prev = [], None
+        for k, (time, time_next) in enumerate(pairs):
+            if time_next < 0:
+                steps.append((time, self._step(host, time, ops.MODE_LAST, clip, cond_scale=cond_scale), 0))
+                continue
+            (_, s0, l0), (a1, s1, l1) = a_s_lam(time), a_s_lam(time_next)
+            h = l1 - l0
+            e = -math.expm1(-h)
+            if k == 0 or k == updating[-1]:
+                c = (a1 * e, s1 / s0, 0.)
+            else:
+                r = h_prev / h
+                c = (a1 * e * (1. + 1. / (2. * r)), s1 / s0, -a1 * e / (2. * r))
+            h_prev = h
+            steps.append((time, self._step(host, time, ops.MODE_MULTISTEP, clip, c, cond_scale), 0))
+        return steps
+
+    def _sampler_steps(self, clip, cond_scale=1.):
+        """the step list of the selected sampler"""
+        return self._dpmpp_steps(clip, cond_scale) if self._check_sampler() == 'dpmpp_2m' else self._ddim_steps(clip, cond_scale)
 
     # hip_graph = True: ONE denoise step of a sampling loop (every kernel of it, on however many HIP streams the network
     # uses) is captured into a HIP graph and replayed once per step; the last step (no noise draw, plus the unnormalise) is

@@ -274,10 +274,11 @@ int dmh_final_conv_nchw(const float* x, const float* w, const float* bias, float
 typedef struct DmhStep {
   int32_t objective;  /* 0 pred_noise, 1 pred_x0, 2 pred_v            CFG:614-628 */
   int32_t clip;       /* clamp x_start to [-1,1]                       CFG:612 */
-  int32_t mode;       /* 0 DDIM update, 1 DDIM last (img = x_start), 2 DDPM posterior step */
+  int32_t mode;       /* 0 DDIM update, 1 DDIM last (img = x_start), 2 DDPM posterior step, 3 multistep (the _ms entry points) */
   float cond_scale;   /* CFG blend null + (cond-null)*s, CFG:410; ignored when model_null == NULL */
   float sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1m_ac; /* extract(..., t) CFG:586-601 */
-  float c0, c1, c2;   /* DDIM: sqrt(alpha_next), c, sigma (CFG:697-707); DDPM: coef1, coef2, exp(.5 logvar) */
+  float c0, c1, c2;   /* DDIM: sqrt(alpha_next), c, sigma (CFG:697-707); DDPM: coef1, coef2, exp(.5 logvar);
+                       * multistep: img' = (c0 * x_start + c1 * img) + c2 * (the previous step's x_start) */
 } DmhStep;
 /* one sampler step on NCHW tensors of n elements: writes img_out and (if non-NULL) x_start, pred_noise.
  * keep (optional, with model_null; per_row = elements of one row): uint8 [n / per_row] — rows with keep == 0 were not computed
@@ -312,6 +313,23 @@ int dmh_sampler_seek(int32_t* cursor, int k, const DmhStep* table, const int64_t
 int dmh_sampler_step_ddp_dev(const DmhStep* cur_dev, const int32_t* cursor, const int32_t* draws, const float* model_out,
                              float* img, const float* noise, const int64_t* sample_ids, uint64_t* state, float* x_start,
                              float* xin_next, int B, int C, int HW, int cpad, int self_cond, void* stream);
+
+/* The step of the second-order multistep solver (DPM-Solver++ 2M in data prediction; not in the reference): mode 3 computes
+ * img_out = (c0 * x_start + c1 * x) + c2 * hist with x_start the clamped data prediction of the entry, exactly the value the
+ * DDIM update uses; mode 1 is the last step as above.  No noise.  hist: [n] floats, the previous step's x_start: each thread
+ * reads its own element when c2 != 0 (an entry with c2 == 0 never reads it: the first step may find anything there) and then
+ * stores the new x_start.  Guided blend, keep / per_row and aliasing of img_out with x as dmh_sampler_step[_dev]; the host-struct
+ * form refuses modes 0 and 2, the device-struct form is validated when the table is built. */
+int dmh_sampler_step_ms(const DmhStep* s, const float* model_cond, const float* model_null, const float* x, float* hist,
+                        float* img_out, float* x_start, int64_t n, const uint8_t* keep, int64_t per_row, void* stream);
+int dmh_sampler_step_ms_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const float* x,
+                            float* hist, float* img_out, float* x_start, int64_t n, const uint8_t* keep, int64_t per_row,
+                            void* stream);
+/* The same step for the UNCONDITIONAL loop in one launch: dmh_sampler_step_ddp_dev without any noise source, draws table or
+ * generator, plus hist [B][C][HW] as above; in place on img, x_start and xin_next (both optional) as there.  cursor: the step
+ * cursor that goes with cur_dev (required like its neighbour's; the entry itself is *cur_dev). */
+int dmh_sampler_step_ddp_ms_dev(const DmhStep* cur_dev, const int32_t* cursor, const float* model_out, float* img, float* hist,
+                                float* x_start, float* xin_next, int B, int C, int HW, int cpad, int self_cond, void* stream);
 
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.

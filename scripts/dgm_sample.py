@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -9,6 +9,8 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
   * -c names results/model-<c>.pt like the reference; when the file does not exist the seeded random
     initialisation is used (the trained DGM.pt lives on HuggingFace, README:8);
   * the loop stops after --batches batches instead of running until killed (SAMPLE:62);
+  * --sampler dpmpp_2m replaces the DDIM update with the second-order multistep solver (an addition: the reference has
+    DDIM only); the default, ddim, is the reference's loop;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -50,6 +52,9 @@ parser.add_argument('--batches', type=int, default=2)
 parser.add_argument('--conditions', type=str, default=None)
 parser.add_argument('--preview', action='store_true', help='write preview sheets when the step counter is a multiple of 100')
 parser.add_argument('--seed', type=int, default=0, help='noise seed (every value is keyed by seed and global sample index)')
+parser.add_argument('--sampler', choices=('ddim', 'dpmpp_2m'), default='ddim',
+                    help="the update over the --s_step time list: the reference's DDIM, or the second-order multistep solver "
+                         "DPM-Solver++ 2M (deterministic, not in the reference; ScheduleHost.sampler)")
 args = parser.parse_args()
 
 num_classes = 1
@@ -77,6 +82,7 @@ def main():
     sampler = trainer.ema.ema_model                        # what Trainer.sample draws from (DDP:1960)
     sampler.model.cfg_mode = 'streams'
     sampler.hip_graph = True                               # one captured denoise step replayed s_step times
+    sampler.sampler = args.sampler
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
