@@ -23,6 +23,7 @@
 #include "common.h"
 
 #include "conv_args.h"
+#include "weight_image.h"
 
 template <int KH, int KW, int S, int UPS, int KC, int TH, int TW>
 struct ConvCfg {
@@ -270,29 +271,10 @@ __global__ void pack_conv_weight_kernel(const float* __restrict__ w, float* __re
   wp[idx] = val;
 }
 
-// N1: per-output-channel weight standardisation (two-pass, one workgroup per channel)
+// N1: per-output-channel weight standardisation (one workgroup per channel; weight_image.h)
 __global__ __launch_bounds__(256) void ws_standardize_kernel(const float* __restrict__ w, float* __restrict__ out,
                                                              int K, float eps) {
-  __shared__ float red[8];
-  const int o = blockIdx.x;
-  const float* wr = w + (size_t)o * K;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < K; i += 256) s += wr[i];
-  for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)K;
-  float q = 0.f;
-  for (int i = threadIdx.x; i < K; i += 256) {
-    const float d = wr[i] - mean;
-    q = fmaf(d, d, q);
-  }
-  for (int off = 32; off; off >>= 1) q += __shfl_xor(q, off);
-  if ((threadIdx.x & 63) == 0) red[4 + (threadIdx.x >> 6)] = q;
-  __syncthreads();
-  const float var = (red[4] + red[5] + red[6] + red[7]) / (float)K;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  for (int i = threadIdx.x; i < K; i += 256) out[(size_t)o * K + i] = (wr[i] - mean) * rstd;
+  ws_standardize_row(w + (size_t)blockIdx.x * K, out + (size_t)blockIdx.x * K, K, eps);
 }
 
 // ------------------------------------------------------------------------------ host side

@@ -59,6 +59,7 @@
 #include "common.h"
 
 #include "conv_args.h"
+#include "weight_image.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -597,82 +598,44 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs p) {
 #undef STAMP
 
 // ------------------------------------------------------------------------------ weight packing
-// per-output-channel scale: 2^k with max |w| * 2^k in [2^14, 2^15); oscale[c] = 2^-k (1 for padded / all-zero channels)
+// The image (weight_image.h: element order, channel scale, the two pieces) of a plain stride-1 weight is made by the
+// table-driven kernels below, one job or many.  The two kernels here serve the forms that re-index the weight:
+// s2d: w is the 4x4 / stride-2 weight [Cout][C0][4][4]; the packed conv is 2x2 over 4*C0 channels ordered (py, px, c):
+//      W2[o][(py, px, c)][dy][dx] = w[o][c][2*dy + py][2*dx + px]   (nch = 4 * C0 / 32 chunks)
+// else the 7x7 with C0 <= 16: one chunk, K slot k = (tap parity) * 16 + channel of tap pair `tap`
 __global__ __launch_bounds__(64) void f16x3_wscale_kernel(const float* __restrict__ w, float* __restrict__ oscale,
                                                            int Cout, int K) {
   const int o = blockIdx.x;
   float m = 0.f;
   if (o < Cout)
     for (int i = threadIdx.x; i < K; i += 64) m = fmaxf(m, fabsf(w[(size_t)o * K + i]));
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if (threadIdx.x == 0) {
-    float s = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      frexpf(m, &e);  // m = f * 2^e, f in [0.5, 1)  ->  m * 2^(15 - e) in [2^14, 2^15)
-      s = ldexpf(1.f, min(max(e - 15, -100), 100));
-    }
-    oscale[o] = s;
-  }
+  const float s = f16x3_row_scale(m);
+  if (threadIdx.x == 0) oscale[o] = s;
 }
 
-// fp16 element index: ((((((nt * nchunks + ch) * NTAPS + tap) * 2 + nh) * 2 + nb) * 2 + plane) * 64 + lane) * 8 + j
-//   -> plane (g1, g2) of w[o = nt*64 + nh*32 + nb*16 + (lane & 15)][c = chunk channel (lane >> 4)*8 + j][tap] * 2^k
-// s2d: w is the 4x4 / stride-2 weight [Cout][C0][4][4]; the packed conv is 2x2 over 4*C0 channels ordered (py, px, c):
-//      W2[o][(py, px, c)][dy][dx] = w[o][c][2*dy + py][2*dx + px]   (nch0 = 4 * C0 / 32 chunks)
 __global__ void pack_f16x3_weight_kernel(const float* __restrict__ w, const float* __restrict__ oscale,
-                                         _Float16* __restrict__ wp, int Cout, int C0, int C1, int NTAPS, int nch0,
-                                         int nch1, int64_t total, int s2d, int pk) {
+                                         _Float16* __restrict__ wp, int Cout, int C0, int NTAPS, int nch, int64_t total,
+                                         int s2d) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
-  int64_t r = idx;
-  const int j = r % 8;
-  r /= 8;
-  const int lane = r % 64;
-  r /= 64;
-  const int plane = r % 2;
-  r /= 2;
-  const int nb = r % 2;
-  r /= 2;
-  const int nh = r % 2;
-  r /= 2;
-  const int tap = r % NTAPS;
-  r /= NTAPS;
-  const int ch = r % (nch0 + nch1);
-  const int nt = r / (nch0 + nch1);
-  const int o = nt * 64 + nh * 32 + nb * 16 + (lane & 15);
-  const int k = (lane >> 4) * 8 + j;
-  int c;
-  bool ok;
-  if (ch < nch0) {
-    c = ch * KC + k;
-    ok = c < C0;
-  } else {
-    c = (ch - nch0) * KC + k;
-    ok = c < C1;
-    c += C0;
-  }
+  const F16x3Slot s = f16x3_slot(idx, NTAPS, nch);
   float ws = 0.f;
   if (s2d) {
-    const int nchc = C0 / KC, par = ch / nchc;
-    const int cr = (ch - par * nchc) * KC + k;  // real input channel
-    const int ky = 2 * (tap >> 1) + (par >> 1), kx = 2 * (tap & 1) + (par & 1);
-    if (o < Cout) ws = w[((size_t)o * C0 + cr) * 16 + ky * 4 + kx] / oscale[o];
-  } else if (pk) {  // 7x7, C0 <= 16: K slot k = (tap parity) * 16 + channel of tap pair `tap`
-    const int tt = 2 * tap + (k >> 4), cc = k & 15;
-    if (o < Cout && cc < C0 && tt < 49) ws = w[((size_t)o * C0 + cc) * 49 + tt] / oscale[o];
-  } else if (ok && o < Cout) {
-    ws = w[((size_t)o * (C0 + C1) + c) * NTAPS + tap] / oscale[o];  // exact: a power of two
+    const int nchc = C0 / KC, par = s.ch / nchc;
+    const int cr = (s.ch - par * nchc) * KC + s.k;  // real input channel
+    const int ky = 2 * (s.tap >> 1) + (par >> 1), kx = 2 * (s.tap & 1) + (par & 1);
+    if (s.o < Cout) ws = w[((size_t)s.o * C0 + cr) * 16 + ky * 4 + kx] / oscale[s.o];  // exact: a power of two
+  } else {
+    const int tt = 2 * s.tap + (s.k >> 4), cc = s.k & 15;
+    if (s.o < Cout && cc < C0 && tt < 49) ws = w[((size_t)s.o * C0 + cc) * 49 + tt] / oscale[s.o];
   }
-  const _Float16 g1 = (_Float16)ws;
-  const _Float16 g2 = (_Float16)(ws - (float)g1);
-  wp[idx] = plane == 0 ? g1 : g2;
+  wp[idx] = f16x3_piece(ws, s.plane);
 }
 
-// ------------------------------------------------------------------------------ many weights at once (training re-pack)
-// dmh_pack_conv_weights_multi: the three phases of ws_standardize -> f16x3_wscale -> pack_f16x3_weight as table-driven
-// kernels over up to PM_MAX jobs per launch (the table travels as a kernel argument: HIP-graph capturable, no device table
-// to keep in step with the caller's buffers).  Plain stride-1 1x1 / 3x3 images only.
+// ------------------------------------------------------------------------------ plain images, one or many at once
+// dmh_pack_conv_weights_multi / the plain form of dmh_pack_conv_weight: three phases — standardise where a job asks for it,
+// channel scales, image elements — as table-driven kernels over up to PM_MAX jobs per launch (the table travels as a kernel
+// argument: HIP-graph capturable, no device table to keep in step with the caller's buffers).
 static int64_t f16x3_frag_floats(int Cout, int C0, int C1, int KH, int KW);
 #define PM_MAX 32
 struct PmTable {
@@ -696,52 +659,24 @@ __device__ __forceinline__ int pm_find(const PmTable& t, int blk) {
 __device__ __forceinline__ float pm_elem(const float* w, int o, int c, int tap, int Cout, int Cin, int T, int tr) {
   return tr ? w[((size_t)c * Cout + o) * T + (T - 1 - tap)] : w[((size_t)o * Cin + c) * T + tap];
 }
-// phase 1: one block per (job, source output channel) — ws_standardize_kernel of conv.hip, same order of operations
+// phase 1: one block per (job, source output channel)
 __global__ __launch_bounds__(256) void pm_ws_kernel(PmTable t, float eps) {
-  __shared__ float red[8];
   const int ti = pm_find(t, blockIdx.x), o = blockIdx.x - t.blk0[ti];
   const int K = (t.tr[ti] ? t.Cout[ti] : t.C0[ti] + t.C1[ti]) * t.T[ti];   // (a job's ws is in the SOURCE layout)
-  const float* wr = t.src[ti] + (size_t)o * K;
-  float* out = t.ws[ti] + (size_t)o * K;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < K; i += 256) s += wr[i];
-  for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)K;
-  float q = 0.f;
-  for (int i = threadIdx.x; i < K; i += 256) {
-    const float d = wr[i] - mean;
-    q = fmaf(d, d, q);
-  }
-  for (int off = 32; off; off >>= 1) q += __shfl_xor(q, off);
-  if ((threadIdx.x & 63) == 0) red[4 + (threadIdx.x >> 6)] = q;
-  __syncthreads();
-  const float var = (red[4] + red[5] + red[6] + red[7]) / (float)K;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  for (int i = threadIdx.x; i < K; i += 256) out[i] = (wr[i] - mean) * rstd;
+  ws_standardize_row(t.src[ti] + (size_t)o * K, t.ws[ti] + (size_t)o * K, K, eps);
 }
-// phase 2: one 64-thread block per (job, padded output channel) — f16x3_wscale_kernel
+// phase 2: one 64-thread block per (job, padded output channel)
 __global__ __launch_bounds__(64) void pm_wscale_kernel(PmTable t) {
   const int ti = pm_find(t, blockIdx.x), o = blockIdx.x - t.blk0[ti];
   const int Cout = t.Cout[ti], Cin = t.C0[ti] + t.C1[ti], T = t.T[ti], tr = t.tr[ti], K = Cin * T;
   const float* w = t.ws[ti] ? t.ws[ti] : t.src[ti];
-  float* oscale = t.wpack[ti] + f16x3_frag_floats_dev(Cout, t.C0[ti], t.C1[ti], T);
   float m = 0.f;
   if (o < Cout)
     for (int i = threadIdx.x; i < K; i += 64) m = fmaxf(m, fabsf(pm_elem(w, o, i / T, i % T, Cout, Cin, T, tr)));
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if (threadIdx.x == 0) {
-    float sc = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      frexpf(m, &e);
-      sc = ldexpf(1.f, min(max(e - 15, -100), 100));
-    }
-    oscale[o] = sc;
-  }
+  const float sc = f16x3_row_scale(m);
+  if (threadIdx.x == 0) t.wpack[ti][f16x3_frag_floats_dev(Cout, t.C0[ti], t.C1[ti], T) + o] = sc;
 }
-// phase 3: 256 fp16 elements of an image per block — pack_f16x3_weight_kernel (plain form)
+// phase 3: 2048 consecutive fp16 elements of an image per block; a source's channels fill whole chunks, zero beyond its width
 __global__ __launch_bounds__(256) void pm_pack_kernel(PmTable t) {
   const int ti = pm_find(t, blockIdx.x);
   const int Cout = t.Cout[ti], C0 = t.C0[ti], C1 = t.C1[ti], T = t.T[ti], tr = t.tr[ti];
@@ -751,41 +686,15 @@ __global__ __launch_bounds__(256) void pm_pack_kernel(PmTable t) {
   const float* w = t.ws[ti] ? t.ws[ti] : t.src[ti];
   const float* oscale = t.wpack[ti] + frag;
   _Float16* wp = reinterpret_cast<_Float16*>(t.wpack[ti]);
-  // (a block covers PM_PACK_PER_BLOCK consecutive elements)
   const int64_t base = (int64_t)(blockIdx.x - t.blk0[ti]) * 2048;
   for (int64_t idx = base + threadIdx.x; idx < min(base + 2048, total); idx += 256) {
-    int64_t r = idx;
-    const int j = r % 8;
-    r /= 8;
-    const int lane = r % 64;
-    r /= 64;
-    const int plane = r % 2;
-    r /= 2;
-    const int nb = r % 2;
-    r /= 2;
-    const int nh = r % 2;
-    r /= 2;
-    const int tap = r % T;
-    r /= T;
-    const int ch = r % (nch0 + nch1);
-    const int nt = r / (nch0 + nch1);
-    const int o = nt * 64 + nh * 32 + nb * 16 + (lane & 15);
-    const int k = (lane >> 4) * 8 + j;
-    int c;
-    bool ok;
-    if (ch < nch0) {
-      c = ch * KC + k;
-      ok = c < C0;
-    } else {
-      c = (ch - nch0) * KC + k;
-      ok = c < C1;
-      c += C0;
-    }
+    const F16x3Slot s = f16x3_slot(idx, T, nch0 + nch1);
+    const bool src1 = s.ch >= nch0;
+    const int c = (s.ch - (src1 ? nch0 : 0)) * KC + s.k;
     float ws = 0.f;
-    if (ok && o < Cout) ws = pm_elem(w, o, c, tap, Cout, C0 + C1, T, tr) / oscale[o];  // exact: a power of two
-    const _Float16 g1 = (_Float16)ws;
-    const _Float16 g2 = (_Float16)(ws - (float)g1);
-    wp[idx] = plane == 0 ? g1 : g2;
+    if (c < (src1 ? C1 : C0) && s.o < Cout)
+      ws = pm_elem(w, s.o, c + (src1 ? C0 : 0), s.tap, Cout, C0 + C1, T, tr) / oscale[s.o];  // exact: a power of two
+    wp[idx] = f16x3_piece(ws, s.plane);
   }
 }
 
@@ -839,16 +748,16 @@ int64_t dmh_f16x3_pack_floats(int Cout, int C0, int C1, int KH, int KW) {
 
 int dmh_f16x3_pack(const float* w, float* wpack, int Cout, int C0, int C1, int KH, int KW, hipStream_t st) {
   const bool s2d = KH == 4;
-  const int nch0 = s2d ? 4 * C0 / KC : cdiv(C0, KC), nch1 = s2d ? 0 : cdiv(C1, KC);
+  if (!s2d && !f16x3_pk(C0, C1, KH)) {  // the plain form: a table of one job
+    const DmhPackJob job = {w, nullptr, wpack, Cout, C0, C1, KH, 0};
+    return dmh_f16x3_pack_multi(&job, 1, 0.f, st);
+  }
   const int64_t frag = f16x3_frag_floats(Cout, C0, C1, KH, KW);
   float* oscale = wpack + frag;
-  hipLaunchKernelGGL(f16x3_wscale_kernel, dim3(cdiv(Cout, 64) * 64), dim3(64), 0, st, w, oscale, Cout,
-                     (C0 + C1) * KH * KW);
+  hipLaunchKernelGGL(f16x3_wscale_kernel, dim3(cdiv(Cout, 64) * 64), dim3(64), 0, st, w, oscale, Cout, C0 * KH * KW);
   const int64_t total = frag * 2;  // fp16 elements
-  const bool pk = f16x3_pk(C0, C1, KH);
   hipLaunchKernelGGL(pack_f16x3_weight_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, w, oscale,
-                     reinterpret_cast<_Float16*>(wpack), Cout, C0, C1, s2d ? 4 : (pk ? 25 : KH * KW), nch0, nch1, total,
-                     s2d ? 1 : 0, pk ? 1 : 0);
+                     reinterpret_cast<_Float16*>(wpack), Cout, C0, s2d ? 4 : 25, s2d ? 4 * C0 / KC : 1, total, s2d ? 1 : 0);
   DMH_CHECK_LAUNCH("dmh_pack_conv_weight(f16x3)");
   return DMH_OK;
 }

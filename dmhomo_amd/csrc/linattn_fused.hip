@@ -20,6 +20,7 @@
 //          the B operand of out^T = ctx^T q^T, whose A operand (the head's context) is split once per workgroup.
 
 #include "common.h"
+#include "weight_image.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -1152,14 +1153,8 @@ __global__ __launch_bounds__(64) void linattn_wscale_kernel(const float* __restr
   const int row = blockIdx.x;  // 0..383
   float m = 0.f;
   for (int i = threadIdx.x; i < C; i += 64) m = fmaxf(m, fabsf(w[(size_t)row * C + i]));
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  const float s = f16x3_row_scale(m);  // (weight_image.h: the conv weights' rule)
   if (threadIdx.x == 0) {
-    float s = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      frexpf(m, &e);
-      s = ldexpf(1.f, min(max(e - 15, -100), 100));
-    }
     if (row < 128) {
       osc_q[row] = s;
     } else {

@@ -57,12 +57,11 @@ class UnetEngine:
         if dev.type != 'cuda':
             raise RuntimeError('dmhomo_amd: the UNet must live on the GPU (call .cuda()); there is no CPU path')
         f32 = lambda k: sd[k].to(torch.float32).contiguous()
+        pb = ops.PackBatch()       # every conv image of this weight version: registered below, made by one run() at the end
 
-        def conv(w, b, c0, c1=0, ws=False, stride=1, ups=0):
-            w = f32(w)
-            if ws:
-                w = ops.ws_standardize(w)
-            return ops.PackedConv(w, None if b is None else f32(b), c0, c1, stride, ups)
+        def conv(w, b, c0, c1=0, ws=False, stride=1, ups=0):     # ws: the batch standardises w into a buffer of its own (N1)
+            w, b = f32(w), None if b is None else f32(b)
+            return ops.PackedConv(torch.empty_like(w) if ws else w, b, c0, c1, stride, ups, batch=pb, ws_from=w if ws else None)
 
         L = unet_layout(sd)
         self.dim, self.has_classes = L.dim, L.has_classes
@@ -88,7 +87,7 @@ class UnetEngine:
             wp = torch.zeros((w0.shape[0], self.cin_pad, 7, 7), device=dev, dtype=torch.float32)
             wp[:, :self.cin] = w0
             w0 = wp
-        self.init_conv = ops.PackedConv(w0, f32('init_conv.bias'), self.cin_pad)
+        self.init_conv = ops.PackedConv(w0, f32('init_conv.bias'), self.cin_pad, batch=pb)
 
         def res(n):
             r, k = _Res(), n.keys
@@ -127,10 +126,11 @@ class UnetEngine:
                 b = attn(n)
             elif n.kind == 'unshuffle':                        # pixel-unshuffle + 1x1  == 2x2 / stride 2
                 w22 = f32(k['w']).reshape(n.cout, n.c0, 2, 2).contiguous()     # channel index = c*4 + p1*2 + p2 (DDP:112)
-                b = ops.PackedConv(w22, f32(k['b']), n.c0, 0, stride=2)
+                b = ops.PackedConv(w22, f32(k['b']), n.c0, 0, stride=2, batch=pb)
             else:
                 b = conv(k['w'], k['b'], n.c0, stride=2 if n.kind == 'down4' else 1, ups=1 if n.kind == 'up3' else 0)
             self.blocks.append((n, b))
+        pb.run()
         # a res block followed by a fused LinearAttention hands it the LayerNorm statistics of its output
         nxt = [b for _, b in self.blocks[1:]] + [None]
         self._pixel_stats = [isinstance(a, _Attn) and a.pla is not None for a in nxt]

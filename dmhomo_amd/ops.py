@@ -21,19 +21,21 @@ def _empty(shape, like, dtype=F32):
 
 
 # ------------------------------------------------------------------ weight preparation
-def ws_standardize(w, eps=1e-5):
+def ws_standardize(w, eps=1e-5, out=None):
     """N1: (w - mean_o) * rsqrt(var_o + eps) per output channel (CFG:123-126)."""
     w = w.detach().contiguous()
-    out = torch.empty_like(w)
+    out = torch.empty_like(w) if out is None else out
     cout = w.shape[0]
     call('dmh_ws_standardize', ptr(w), ptr(out), cout, w.numel() // cout, float(eps))
     return out
 
 
 class PackBatch:
-    """the weights a training step re-packs after every optimiser update, as ONE table for dmh_pack_conv_weights_multi
-    (three kernel phases over all of them) + the few that need their own launches (``specials``: closures that pack into
-    buffers allocated once).  Buffers and source pointers are fixed when the batch is built; ``run()`` is graph-capturable."""
+    """the weight images of many PackedConvs, made together by ``run()`` — now and again after every update of the weights
+    (a training step re-packs after every optimiser step): ``pre`` (closures that assemble a weight from the parameters:
+    padded, re-indexed, standardised), then ONE table for dmh_pack_conv_weights_multi (three kernel phases over all plain
+    stride-1 1x1 / 3x3 images), then ``specials`` (the images that need launches of their own).  Buffers and source
+    pointers are fixed when the batch is built; ``run()`` is graph-capturable."""
 
     def __init__(self):
         self.jobs, self.pre, self.specials, self._keep, self._arr = [], [], [], [], None
@@ -44,7 +46,7 @@ class PackBatch:
         self._arr = None
 
     def run(self, eps=1e-5):
-        for f in self.pre:                 # (weights that are first assembled from the parameters: padded, re-indexed)
+        for f in self.pre:
             f()
         if self.jobs:
             if self._arr is None:
@@ -59,22 +61,26 @@ def f16x3_default():
     return os.environ.get('DMH_CONV3_VARIANT', '9') == '9'
 
 
-def _batchable(kh, stride, upsample2):
-    # (dmh_pack_conv_weights_multi makes the fp16-piece images of the default kernels only)
-    return kh in (1, 3) and stride == 1 and not upsample2 and f16x3_default()
-
-
 class PackedConv:
-    """a conv weight in dmh_conv2d's tile-major layout + its geometry.
-    batch (PackBatch): the image is NOT made here but by ``batch.run()`` — from ``w_oihw`` (whose storage must stay where
-    it is), or, with ``ws_from`` (the raw weight), from its standardised form, which the batch writes into ``w_oihw``."""
+    """a conv weight in dmh_conv2d's tile-major layout + its geometry.  How the image is made is decided here and nowhere
+    else; every route goes through a PackBatch (``batch``; a private one, run before the constructor returns, when None):
+    the plain stride-1 1x1 / 3x3 images of the default kernels are jobs of its table, every other form (7x7, 4x4 and
+    2x2 / stride 2, sub-pixel Upsample + 3x3, all of them under the exact-fp32 DMH_CONV3_VARIANT 0 / 6) registers ``repack``
+    with it.  tests/test_gpu_weight_image.py pins the table's images to the single launches' and to the documented layout.
+    With a ``batch`` the image exists after ``batch.run()``; ``w_oihw``'s storage must stay where it is.
+    ws_from (the raw weight): the image is that of its standardised form, which the batch also writes into ``w_oihw``.
+    transposed: ``w_oihw`` is the weight (c0, Cout, k, k) of a stride-1 conv and the image is that of its DATA-GRADIENT conv
+    (taps flipped, O and I exchanged: by index arithmetic in the table's kernels, through a copy otherwise)."""
     __slots__ = ('wpack', 'bias', 'cout', 'c0', 'c1', 'k', 'stride', 'upsample2', '_w', '_up2')
 
-    def __init__(self, w_oihw, bias, c0, c1=0, stride=1, upsample2=0, subpixel=True, batch=None, ws_from=None):
+    def __init__(self, w_oihw, bias, c0, c1=0, stride=1, upsample2=0, subpixel=True, batch=None, ws_from=None,
+                 transposed=False):
         w = w_oihw.detach()
         assert w.is_contiguous()
         cout, cin, kh, kw = w.shape
-        assert cin == c0 + c1 and kh == kw, (w.shape, c0, c1)
+        if transposed:
+            cout, cin = cin, cout
+        assert cin == c0 + c1 and kh == kw and not (transposed and (c1 or stride != 1 or upsample2)), (w.shape, c0, c1)
         self._w = w
         n_up2 = lib().dmh_conv_up2_pack_floats(cout, c0) if (upsample2 and kh == 3 and c1 == 0 and subpixel) else -1
         self._up2 = n_up2 > 0
@@ -85,19 +91,25 @@ class PackedConv:
             self.wpack = _empty((lib().dmh_conv_pack_floats(cout, c0, c1, kh, kw),), w)
         self.bias = None if bias is None else bias.detach().contiguous()
         self.cout, self.c0, self.c1, self.k, self.stride, self.upsample2 = cout, c0, c1, kh, stride, upsample2
-        if batch is not None and _batchable(kh, stride, upsample2):
-            if ws_from is not None:
-                batch.add(ws_from.detach(), w, self.wpack, cout, c0, c1, kh, 0)
-            else:
-                batch.add(w, None, self.wpack, cout, c0, c1, kh, 0)
+        own = batch is None
+        if own:
+            batch = PackBatch()
+        src = None if ws_from is None else ws_from.detach()
+        assert src is None or (src.is_contiguous() and src.shape == w.shape)
+        if kh in (1, 3) and stride == 1 and not upsample2 and f16x3_default():
+            batch.add(w if src is None else src, None if src is None else w, self.wpack, cout, c0, c1, kh, transposed)
         else:
-            assert ws_from is None
-            if batch is not None:
-                batch.specials.append(self.repack)
-            self.repack()
+            if src is not None:
+                batch.pre.append(lambda: ws_standardize(src, out=w))
+            if transposed:
+                self._w = wt = _empty((cout, cin, kh, kw), w)
+                batch.pre.append(lambda: wt.copy_(w.flip(2, 3).transpose(0, 1)))
+            batch.specials.append(self.repack)
+        if own:
+            batch.run()
 
     def repack(self):
-        """(re)make the image from the weight tensor's current values"""
+        """(re)make an image that has launches of its own from the weight tensor's current values"""
         if self._up2:
             call('dmh_pack_conv_weight_up2', ptr(self._w), ptr(self.wpack), self.cout, self.c0)
         else:
@@ -778,33 +790,11 @@ def conv_wgrad(dy, src0, src1=None, k=3, in_coef=None, want_bias=True, ups=0):
     return (dw, db) if want_bias else dw
 
 
-class _DgradPacked(PackedConv):
-    """the data-gradient conv of a stride-1 conv with weight w, its image made by a PackBatch from w itself (taps flipped
-    and (Cout, Cin) exchanged by index arithmetic in the pack kernel: no flipped / transposed copy of the weight)"""
-    __slots__ = ()
-
-    def __init__(self, w, c_in_total, batch):
-        w = w.detach()
-        cout_src, cin_src, kh, kw = w.shape
-        assert cin_src == c_in_total and kh == kw and w.is_contiguous()
-        self._w, self._up2 = w, False
-        self.wpack = _empty((lib().dmh_conv_pack_floats(cin_src, cout_src, 0, kh, kw),), w)
-        self.bias = None
-        self.cout, self.c0, self.c1, self.k, self.stride, self.upsample2 = cin_src, cout_src, 0, kh, 1, 0
-        batch.add(w, None, self.wpack, cin_src, cout_src, 0, kh, 1)
-
-
 def conv_dgrad_pack(w, c_in_total, batch=None):
     """PackedConv that computes the DATA gradient of a stride-1 conv with weight w (Cout, Cin, k, k): the same conv
     kernel on dy with the taps flipped and (Cout, Cin) transposed (no bias)."""
-    if batch is not None and _batchable(w.shape[-1], 1, 0):
-        return _DgradPacked(w, c_in_total, batch)
-    wt = w.detach().flip(2, 3).transpose(0, 1).contiguous()          # (Cin, Cout, k, k)
-    assert wt.shape[0] == c_in_total
-    if batch is not None:            # (exact-fp32 variants: no table-driven pack) re-made from w on every batch.run()
-        w_src = w.detach()
-        batch.pre.append(lambda: wt.copy_(w_src.flip(2, 3).transpose(0, 1)))
-    return PackedConv(wt, None, w.shape[0], batch=batch)
+    assert w.shape[1] == c_in_total
+    return PackedConv(w, None, w.shape[0], batch=batch, transposed=True)
 
 
 def gn_finalize_train(stats, gamma, beta, hw, groups, ss=None, eps=1e-5):
