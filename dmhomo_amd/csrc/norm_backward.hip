@@ -12,6 +12,8 @@
 #include "common.h"
 
 #define GNB_PCH 256  // pixels per partial chunk
+// (tests/test_norm_backward_host.py restates the reduce kernel's 256-thread quad / pixel-lane plan to show that each case of
+// tests/norm_bwd_cases.py reaches the branch it names: change the plan and that test together)
 
 // SiLU'(z) = sg * (1 + z * (1 - sg)), sg = sigmoid(z) on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1-2 ulp) like
 // the forward's silu_fast (round 3: the exact expf + IEEE division made the reduce / apply kernels vector-bound — two reads of
@@ -349,6 +351,8 @@ __global__ __launch_bounds__(256) void chan_layernorm_bwd_kernel(const float* __
 }
 
 #define DMH_LNB_BLOCKS 256  // partial dg rows
+// (tests/test_norm_backward_host.py restates the 256-thread workgroup and the <LPP, NV> ladder of
+// dmh_chan_layernorm_backward below for the same purpose: change them and that test together)
 
 template <int LPP, int NV>
 static int launch_lnb(const float* x, const float* g, const float* dout, float* dx, float* dg_part, int64_t npix, int C,
