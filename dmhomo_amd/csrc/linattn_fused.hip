@@ -359,6 +359,8 @@ __global__ __launch_bounds__(256, 2) void linattn_kv_kernel(const float* __restr
     st.begin_tile(stats_b, sp * tiles * TP);
     st.issue(0);
   }
+  // (tiles > 1 from n >= 4096 only; the sizes that reach the rescale across sub-tiles, the prefetch guard and a short last
+  //  split are restated in tests/test_linattn_fused_host.py and run against fp64 by tests/test_gpu_linattn_fused.py)
   for (int tI = 0; tI < tiles; ++tI) {
     const int p0 = (sp * tiles + tI) * TP;
     if (p0 >= n) break;
@@ -606,6 +608,8 @@ __global__ __launch_bounds__(256, 2) void linattn_kv_ring_kernel(const float* __
 #else
 #define KSTAMP(i)
 #endif
+  // (tiles > 1 from n >= 4096 only; the sizes that reach the rescale across sub-tiles, the prefetch guard and a short last
+  //  split are restated in tests/test_linattn_fused_host.py and run against fp64 by tests/test_gpu_linattn_fused.py)
   for (int tI = 0; tI < tiles; ++tI) {
     const int p0 = (sp * tiles + tI) * TP;
     if (p0 >= n) break;
@@ -919,6 +923,7 @@ __global__ __launch_bounds__(256, 2) void linattn_qo_kernel(const float* __restr
 #else
 #define LSTAMP(i)
 #endif
+  // (the sub-tile plan: tests/test_linattn_fused_host.py, as in pass 1)
   for (int tI = 0; tI < tiles; ++tI) {
     const int p0 = (blk * tiles + tI) * TP;
     if (p0 >= n) break;
@@ -1231,6 +1236,8 @@ static int fused_tiles(int B, int n) {
   // sub-tiles per workgroup: a function of n ONLY — the split of a sample's pixels fixes the order of its online-softmax
   // merges, and a sample's result must not depend on how many other samples share the launch (rows stay bitwise
   // independent: what makes sharding across GPUs and the two-stream CFG split exact).
+  // (no export: restated as `plan` in tests/linattn_fused_cases.py and held against dmh_linattn_fused_splits and the case
+  //  table by tests/test_linattn_fused_host.py — a change here moves the pixel counts at which the sub-tile loops are tested)
   (void)B;
   const int nt = cdiv(n, TP);
   const int t = nt / 32;  // (round 2: 32 splits per sample at most — 64 in round 1; swept 8 .. 64: +0.4 % images/s, 64x64 levels -9 %)

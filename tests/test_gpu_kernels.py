@@ -368,7 +368,8 @@ def test_linear_attention_core(ops, H, W):
 @pytest.mark.parametrize('C,H,W', [(64, 16, 16), (64, 7, 9), (128, 24, 40), (256, 8, 8), (64, 40, 56)])
 def test_linear_attention_fused(ops, C, H, W):
     """PreNorm LayerNorm + to_qkv + LinearAttention core in two kernels (q, k, v never stored) against the unfused
-    math in fp64: ragged pixel counts (sub-tiles of 64 pixels, several per workgroup), all channel widths of the UNet"""
+    math in fp64: ragged pixel counts (sub-tiles of 64 pixels, ONE per workgroup at every shape here — a workgroup owns
+    several only from 4096 pixels; those sizes: tests/test_gpu_linattn_fused.py), all channel widths of the UNet"""
     B = 3
     x = rand((B, C, H, W), 40) * 1.7 + 0.3
     x[:, :C // 2] *= 4.0                                   # two channel chunks with different block maxima
