@@ -210,7 +210,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
     def model_predictions(self, x, t, classes, rgb_flow, mask, cond_scale=3., clip_x_start=False):
         """CFG:610-630.  One timestep for the whole batch (what the samplers pass): blend, objective branch and clamp in
-        ONE pass of dmh_sampler_step; a timestep per row (p_losses-style callers): the same arithmetic row by row."""
+        ONE pass of dmh_sampler_step; a timestep per row (p_losses-style callers): the same arithmetic row by row.
+        ``clip_x_start=True`` is the static clamp to [-1, 1] whatever ``clip_mode`` says: dynamic thresholding lives in the
+        sampling loops only."""
         host = self._host()
         cond, null, computed = self._network(x, t, classes, rgb_flow, mask, cond_scale)
         t0 = self._uniform_time(t)
@@ -253,19 +255,34 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         return self._ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale, clip_denoised)
 
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
-        """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests."""
+        """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
+        'dynamic', the step's thresholds 'thr')."""
         batch, device = shape[0], self.betas.device
         steps = self._ddim_steps(clip_denoised, cond_scale)
+        rank = self._dynamic_rank(shape, clip_denoised)
         img = self.rng.randn(shape, device).contiguous()
         for time, step, draws in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
             noise = self.rng.randn(shape, device).contiguous() if draws else None
-            img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
+            if rank is None:
+                img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
+                thr = None
+            else:
+                thr, _ = ops.sampler_threshold(step, cond, null, img, *rank, keep=computed)
+                img, x_start = ops.sampler_step_thr(step, cond, null, img, noise, None, thr, want_x_start=trace is not None,
+                                                    keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, **({} if thr is None else {'thr': thr})})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
+
+    def _dynamic_rank(self, shape, clip):
+        """(k, frac) of the row quantile where the loop thresholds dynamically (clip_mode = 'dynamic' and a clipping loop),
+        else None: the static clamp, the existing step kernels"""
+        if self._check_clip_mode() != 'dynamic' or not clip:
+            return None
+        return self._quantile_rank(float(self.dynamic_threshold_percentile), shape[1] * shape[2] * shape[3])
 
     def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """the loop of _ddim_sample with the multistep solver's update (ScheduleHost._dpmpp_steps; not in the reference): the
@@ -273,14 +290,21 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         x_start in ``hist``.  ``trace`` as _ddim_sample."""
         batch, device = shape[0], self.betas.device
         steps = self._dpmpp_steps(clip_denoised, cond_scale)
+        rank = self._dynamic_rank(shape, clip_denoised)
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         for time, step, _ in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
-            img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
+            if rank is None:
+                img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
+                thr = None
+            else:
+                thr, _ = ops.sampler_threshold(step, cond, null, img, *rank, keep=computed)
+                img, x_start = ops.sampler_step_thr(step, cond, null, img, None, hist, thr, want_x_start=trace is not None,
+                                                    keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, **({} if thr is None else {'thr': thr})})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -317,14 +341,17 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale):
         """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times.
         With sampler = 'dpmpp_2m' the step is the network, dmh_sampler_step_ms_dev on a static history buffer and the seek:
-        no randn launch is left in it."""
+        no randn launch is left in it.  With clip_mode = 'dynamic' the update is two calls, dmh_sampler_threshold_dev and
+        dmh_sampler_step_thr_dev, on a static scratch and a static threshold per row."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
+        rank = self._dynamic_rank(shape, clip)               # None: the static clamp
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
                bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
-               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key(), self.sampler)
+               self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key(), self.sampler,
+               self.clip_mode, None if rank is None else float(self.dynamic_threshold_percentile))
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -336,23 +363,29 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
             if solver:
                 st['hist'] = torch.zeros(shape, device=device)
+            if rank is not None:                             # dynamic thresholding: scratch for the raw x_start, a threshold per row
+                st['x0_raw'] = torch.zeros(shape, device=device)
+                st['thr'] = torch.ones((shape[0],), device=device)
+
+            def step(cond, null, computed, noise, out):      # the update of the entry at the cursor
+                hist = st['hist'] if solver else None
+                if rank is not None:
+                    ops.sampler_threshold_dev(st['cur'], cond, null, st['img'], *rank, keep=computed, x0_raw=st['x0_raw'],
+                                              thr=st['thr'])
+                    return ops.sampler_step_thr_dev(st['cur'], cond, null, st['img'], noise, hist, st['thr'], out=out,
+                                                    keep=computed)
+                if solver:
+                    return ops.sampler_step_ms_dev(st['cur'], cond, null, st['img'], hist, out=out, keep=computed)
+                return ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=out, keep=computed)
 
             def mid():                                       # one denoise step of CFG:684-707, in place on st['img']
-                cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
-                if solver:
-                    ops.sampler_step_ms_dev(st['cur'], cond, null, st['img'], st['hist'], out=st['img'], keep=computed)
-                else:
-                    noise = self.rng.randn(shape, device).contiguous()
-                    ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=st['img'], keep=computed)
+                logits = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
+                step(*logits, None if solver else self.rng.randn(shape, device).contiguous(), st['img'])
                 ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
 
             def last():                                      # CFG:693-695 + unnormalize, CFG:709
-                cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
-                if solver:
-                    x0 = ops.sampler_step_ms_dev(st['cur'], cond, null, st['img'], st['hist'], keep=computed)
-                else:
-                    x0 = ops.sampler_step_dev(st['cur'], cond, null, st['img'], None, keep=computed)
-                return ops.affine(x0, 0.5, 0.5)
+                logits = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
+                return ops.affine(step(*logits, None, None), 0.5, 0.5)
             return mid, last
 
         def fill(st):

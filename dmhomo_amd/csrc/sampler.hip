@@ -5,6 +5,7 @@
 #include "philox.h"
 
 #pragma clang fp contract(off)
+#include "sampler_dev.h"
 
 // out NHWC [reps*B][HW][Cpad] <- cat(a, b*m) zero padded; sample r reads source r % B
 __global__ __launch_bounds__(256) void assemble_input_kernel(const float* __restrict__ a, int Ca,
@@ -129,54 +130,7 @@ __global__ __launch_bounds__(256) void final_conv_kernel(const float* __restrict
   }
 }
 
-// torch.clamp(x, -1., 1.) (CFG:612,634): NaN stays NaN (fminf / fmaxf alone would turn it into -1 and hide a broken row)
-__device__ __forceinline__ float clamp_pm1(float x) { return x != x ? x : fminf(fmaxf(x, -1.f), 1.f); }
-
-// the network output a step works on: model_cond[i], or with model_null the guided null + (cond - null) * cond_scale (CFG:410).
-// keep (with model_null): row i / per_row of model_cond was only computed where keep != 0 — a row whose class the conditional
-// pass dropped (CFG:415-425) has the null pass's inputs, so its logits ARE the null logits and model_cond is never read there
-__device__ __forceinline__ float guided_logit(const float* mc, const float* mn, const uint8_t* keep, int64_t i, int64_t per_row,
-                                              float cond_scale) {
-  if (!mn) return mc[i];
-  const float nl = mn[i];
-  const float mo = (keep && !keep[i / per_row]) ? nl : mc[i];
-  return nl + (mo - nl) * cond_scale;
-}
-
-// ONE denoise step on one element, the only statement of it: every step kernel below calls this, so the eager, the captured
-// and the fused path cannot differ in a bit.  mo: guided_logit, xt: the current image, nz: the entry's noise value, has_noise:
-// whether the DDPM update adds it (a DDIM update always does), prev: the previous step's x0 (read by a multistep entry with
-// c2 != 0 only) -> x0 (x_start), pn (pred_noise), o (the next image)
-__device__ __forceinline__ void denoise_step(const DmhStep& s, float mo, float xt, float nz, bool has_noise, float prev,
-                                             float& x0, float& pn, float& o) {
-  if (s.objective == 0) {  // pred_noise, CFG:614-617
-    pn = mo;
-    x0 = s.sqrt_recip_ac * xt - s.sqrt_recipm1_ac * pn;
-    if (s.clip) x0 = clamp_pm1(x0);
-  } else if (s.objective == 1) {  // pred_x0, CFG:619-622
-    x0 = mo;
-    if (s.clip) x0 = clamp_pm1(x0);
-    pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-  } else {  // pred_v, CFG:624-628
-    x0 = s.sqrt_ac * xt - s.sqrt_1m_ac * mo;
-    if (s.clip) x0 = clamp_pm1(x0);
-    pn = (s.sqrt_recip_ac * xt - x0) / s.sqrt_recipm1_ac;
-  }
-  if (s.mode == 0) {  // DDIM, CFG:705-707
-    o = x0 * s.c0 + s.c1 * pn + s.c2 * nz;
-  } else if (s.mode == 1) {  // last DDIM step, CFG:693-695
-    o = x0;
-  } else if (s.mode == 2) {  // DDPM posterior step, DDP:604-611,660: mean + exp(.5 logvar) * noise (no noise at t == 0)
-    o = s.c0 * x0 + s.c1 * xt;
-    if (has_noise) o = o + s.c2 * nz;
-  } else {  // multistep (DPM-Solver++ 2M, data prediction): c2 == 0 is its first-order update and leaves prev unread
-    o = s.c0 * x0 + s.c1 * xt;
-    if (s.c2 != 0.f) o = o + s.c2 * prev;
-  }
-}
-
-// whether an entry reads the x0 history of the multistep solver
-__device__ __forceinline__ bool reads_history(const DmhStep& s) { return s.mode == 3 && s.c2 != 0.f; }
+// clamp_pm1, guided_logit, raw_x_start, denoise_step, reads_history: sampler_dev.h (shared with threshold.hip)
 
 // the body of the element-per-thread step kernels.  missing: what stands for the noise of an entry that has none, and for the
 // history of a multistep entry that reads one without hist.  hist (the multistep kernels): [n], the previous step's x0 — a

@@ -530,6 +530,73 @@ def sampler_step_ddp_ms_dev(cur, cursor, model_out, img, hist, x_start=None, xin
     return img
 
 
+def row_quantile_abs(x, k, frac, floor=0., out=None):
+    """(B, ...) fp32 -> (B,): max(floor, quantile of |x[b]| at rank k + frac, linearly interpolated) — an exact selection
+    (dmh_row_quantile_abs); a row that holds a NaN answers NaN.  (k, frac): ScheduleHost._quantile_rank(p, n)."""
+    B = x.shape[0]
+    if out is None:
+        out = _empty((B,), x)
+    elif tuple(out.shape) != (B,):
+        raise ValueError(f'row_quantile_abs: out {tuple(out.shape)} for {B} rows')
+    call('dmh_row_quantile_abs', ptr(x), ptr(out), B, x.numel() // max(B, 1), int(k), float(frac), float(floor))
+    return out
+
+
+def _threshold_buffers(who, x, x0_raw, thr):
+    x0_raw = torch.empty_like(x) if x0_raw is None else x0_raw
+    thr = _empty((x.shape[0],), x) if thr is None else thr
+    if tuple(x0_raw.shape) != tuple(x.shape) or tuple(thr.shape) != (x.shape[0],):
+        raise ValueError(f'{who}: x0_raw {tuple(x0_raw.shape)} / thr {tuple(thr.shape)} against x {tuple(x.shape)}')
+    return x0_raw, thr
+
+
+def sampler_threshold(step, model_cond, model_null, x, k, frac, keep=None, x0_raw=None, thr=None):
+    """the dynamic threshold of one denoise step (dmh_sampler_threshold): x0_raw = the step's x_start before any clamp (guided
+    blend with ``keep`` as sampler_step, objective branch), thr[b] = max(1, quantile of |x0_raw[b]| at rank k + frac).
+    -> (thr, x0_raw)"""
+    x0_raw, thr = _threshold_buffers('sampler_threshold', x, x0_raw, thr)
+    call('dmh_sampler_threshold', C.byref(step), ptr(model_cond), ptr(model_null), ptr(x), ptr(keep, torch.uint8), ptr(x0_raw),
+         ptr(thr), x.shape[0], x.numel() // x.shape[0], int(k), float(frac))
+    return thr, x0_raw
+
+
+def sampler_threshold_dev(cur, model_cond, model_null, x, k, frac, keep=None, x0_raw=None, thr=None):
+    """sampler_threshold with its DmhStep in device memory (``cur`` of step_table)"""
+    x0_raw, thr = _threshold_buffers('sampler_threshold_dev', x, x0_raw, thr)
+    call('dmh_sampler_threshold_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(keep, torch.uint8),
+         ptr(x0_raw), ptr(thr), x.shape[0], x.numel() // x.shape[0], int(k), float(frac))
+    return thr, x0_raw
+
+
+def _step_thr_shapes(who, x, noise, hist, thr):
+    for t in (noise, hist):
+        if t is not None and tuple(t.shape) != tuple(x.shape):
+            raise ValueError(f'{who}: {tuple(t.shape)} against x {tuple(x.shape)}')
+    if tuple(thr.shape) != (x.shape[0],):
+        raise ValueError(f'{who}: thr {tuple(thr.shape)} for {x.shape[0]} rows')
+
+
+def sampler_step_thr(step, model_cond, model_null, x, noise, hist, thr, out=None, want_x_start=False, keep=None):
+    """sampler_step / sampler_step_ms with a threshold per row (dmh_sampler_step_thr): where the entry clips, x_start =
+    clamp(x0_raw, -thr[b], thr[b]) / thr[b].  ``noise`` for a DDIM entry, ``hist`` for a multistep entry (the other None).
+    out may be x (in place).  -> (img, x_start or None)"""
+    _step_thr_shapes('sampler_step_thr', x, noise, hist, thr)
+    img = torch.empty_like(x) if out is None else out
+    xs = torch.empty_like(x) if want_x_start else None
+    call('dmh_sampler_step_thr', C.byref(step), ptr(model_cond), ptr(model_null), ptr(x), ptr(noise), ptr(hist), ptr(thr),
+         ptr(img), ptr(xs), x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img, xs
+
+
+def sampler_step_thr_dev(cur, model_cond, model_null, x, noise, hist, thr, out=None, x_start=None, keep=None):
+    """sampler_step_thr with its DmhStep in device memory (``cur`` of step_table); out may be x (in place)."""
+    _step_thr_shapes('sampler_step_thr_dev', x, noise, hist, thr)
+    img = torch.empty_like(x) if out is None else out
+    call('dmh_sampler_step_thr_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(noise), ptr(hist),
+         ptr(thr), ptr(img), ptr(x_start), x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img
+
+
 def rng_indexed(shape, sample_ids, state, kind=0):
     """one draw of the sample-indexed generator (dmh_rng_indexed): (B, *shape[1:]) fp32 whose row b is a pure function of
     (state[0] = seed, sample_ids[b], state[1] = draw index, element); the launch advances the draw index.

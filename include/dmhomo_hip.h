@@ -331,6 +331,40 @@ int dmh_sampler_step_ms_dev(const DmhStep* cur_dev, const float* model_cond, con
 int dmh_sampler_step_ddp_ms_dev(const DmhStep* cur_dev, const int32_t* cursor, const float* model_out, float* img, float* hist,
                                 float* x_start, float* xin_next, int B, int C, int HW, int cpad, int self_cond, void* stream);
 
+/* Dynamic thresholding of x_start (Saharia et al. 2022, "Imagen", 2.3; not in the reference).
+ *
+ * dmh_row_quantile_abs: x [B][n] -> out[b] = max(floor, q_b), q_b the quantile of the n values |x[b][.]| at rank k + frac
+ * with linear interpolation (torch.quantile's): v = the values sorted ascending, a = v[k]; frac == 0 or v[k+1] == a: q = a,
+ * else q = fmaf(v[k+1] - a, frac, a) in fp32.  a and v[k+1] are the EXACT order statistics of the fp32 values (a radix select
+ * on their bit patterns, integer counting only: bitwise repeatable).  A row that holds a NaN answers NaN.  The host turns a
+ * percentile p into k = floor(p * (n - 1)), frac = float(p * (n - 1) - k), in double.  1 <= n < 2^31, 0 <= k < n, 0 <= frac < 1,
+ * k + 1 < n where frac != 0.  One workgroup per row; no workspace.
+ *
+ * dmh_sampler_threshold[_dev]: for one denoise step (DmhStep by value, or read from device memory as dmh_sampler_step_dev
+ * reads it) writes x0_raw [B][n] = the step's x_start before any clamp — the guided blend (model_null, keep as
+ * dmh_sampler_step's, per_row = n) and the objective branch, the same statement the step kernels use — and thr [B] =
+ * max(1, quantile of |x0_raw[b]|) through the selector above.  x0_raw is scratch the caller provides; two launches.
+ *
+ * dmh_sampler_step_thr[_dev]: dmh_sampler_step / dmh_sampler_step_ms with a threshold per row, thr [n / per_row]: where the
+ * entry's clip is set, x_start = clamp(x0_raw, -thr, thr) / thr instead of clamp(x0_raw, -1, 1) (thr == 1: the same bits;
+ * thr NaN: the row becomes NaN); with clip == 0 thr is not read.  Everything behind the clamp is the step as it stands.
+ * noise (a DDIM entry, mode 0) and hist (a multistep entry, mode 3; read where c2 != 0, then overwritten with the new
+ * x_start) are optional and exclude each other; mode 1 needs neither; the host-struct form refuses mode 2 and an entry
+ * without the buffer it reads, the device-struct form answers NaN there.  img_out may alias x. */
+int dmh_row_quantile_abs(const float* x, float* out, int B, int64_t n, int64_t k, float frac, float floor, void* stream);
+int dmh_sampler_threshold(const DmhStep* s, const float* model_cond, const float* model_null, const float* x,
+                          const uint8_t* keep, float* x0_raw, float* thr, int B, int64_t n, int64_t k, float frac,
+                          void* stream);
+int dmh_sampler_threshold_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const float* x,
+                              const uint8_t* keep, float* x0_raw, float* thr, int B, int64_t n, int64_t k, float frac,
+                              void* stream);
+int dmh_sampler_step_thr(const DmhStep* s, const float* model_cond, const float* model_null, const float* x,
+                         const float* noise, float* hist, const float* thr, float* img_out, float* x_start, int64_t n,
+                         const uint8_t* keep, int64_t per_row, void* stream);
+int dmh_sampler_step_thr_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const float* x,
+                             const float* noise, float* hist, const float* thr, float* img_out, float* x_start, int64_t n,
+                             const uint8_t* keep, int64_t per_row, void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -11,6 +11,9 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
   * the loop stops after --batches batches instead of running until killed (SAMPLE:62);
   * --sampler dpmpp_2m replaces the DDIM update with the second-order multistep solver (an addition: the reference has
     DDIM only); the default, ddim, is the reference's loop;
+  * --clip_mode dynamic replaces the clamp of every step's x_start to [-1, 1] by dynamic thresholding at the
+    --dynamic_threshold_percentile-th percentile of each sample's |x_start| (an addition: the reference clamps); the default,
+    static, is the reference's clamp;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -55,6 +58,11 @@ parser.add_argument('--seed', type=int, default=0, help='noise seed (every value
 parser.add_argument('--sampler', choices=('ddim', 'dpmpp_2m'), default='ddim',
                     help="the update over the --s_step time list: the reference's DDIM, or the second-order multistep solver "
                          "DPM-Solver++ 2M (deterministic, not in the reference; ScheduleHost.sampler)")
+parser.add_argument('--clip_mode', choices=('static', 'dynamic'), default='static',
+                    help="what a step does to x_start: the reference's clamp to [-1, 1], or dynamic thresholding (Saharia et al. "
+                         "2022; not in the reference; ScheduleHost.clip_mode)")
+parser.add_argument('--dynamic_threshold_percentile', type=float, default=0.995,
+                    help='the percentile of |x_start| per sample that --clip_mode dynamic clamps at, in (0, 1]')
 args = parser.parse_args()
 
 num_classes = 1
@@ -83,6 +91,7 @@ def main():
     sampler.model.cfg_mode = 'streams'
     sampler.hip_graph = True                               # one captured denoise step replayed s_step times
     sampler.sampler = args.sampler
+    sampler.clip_mode, sampler.dynamic_threshold_percentile = args.clip_mode, args.dynamic_threshold_percentile
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
