@@ -10,6 +10,8 @@
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
+// (both restated in tests/attn_core_cases.py; tests/test_attn_core_host.py holds the restatement to dmh_linattn_splits and
+//  dmh_linattn_partial_floats)
 #define LA_NS 128                  // pixels per split of linattn pass 1
 #define LA_PART (32 + 32 + 1024)   // per (b, split, head): max[32], sum[32], ctx[32][32]
 
@@ -30,12 +32,15 @@ __global__ __launch_bounds__(256) void linattn_context_kernel(const float* __res
   // the split's k AND v values are all requested up front (128 independent loads in flight per wave) and
   // live in registers: the matrix loop below then never waits on memory
   float kr[LA_NS / 2], vr[LA_NS / 2];
-  const float* kp = base + (size_t)p0 * 384 + 128 + h * 32 + d + (size_t)half * 384;
+  const float* k0 = base + (size_t)p0 * 384 + 128 + h * 32 + d;  // the split's first pixel: always inside qkv
+  const float* kp = k0 + (size_t)half * 384;
 #pragma unroll
   for (int i = 0; i < LA_NS / 2; ++i) {
     const int pix = p0 + 2 * i + half;
     const bool ok = pix < n;
-    const float* q = ok ? kp + (size_t)i * 768 : kp;  // clamped address, masked value: no branch around a load
+    // clamped address, masked value: no branch around a load.  (Clamped to k0, not kp: a last split of ONE pixel has no
+    // pixel p0 + 1, and kp of the upper lane half would lie past the end of the last row's qkv.)
+    const float* q = ok ? kp + (size_t)i * 768 : k0;
     const float kv = q[0], vv = q[128];
     kr[i] = ok ? kv : -INFINITY;
     vr[i] = ok ? vv : 0.f;  // here d plays e
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(1024) void linattn_merge_kernel(const float* __rest
 
 // pass 2: out[p][h*32+e] = sum_d ctx[d][e] * q'[p][d],  q' = softmax_d(q[p]) * scale.
 // K-slot map: lane half h, step s  <->  d = 16*half + s  (each lane loads 16 contiguous floats).
-#define LA_TILES 4  // 32-pixel tiles per wave
+#define LA_TILES 4  // 32-pixel tiles per wave (no export; tests/test_gpu_attn_core.py runs n = 127 ... 129 around one block)
 __global__ __launch_bounds__(256) void linattn_apply_kernel(const float* __restrict__ qkv,
                                                             const float* __restrict__ ctx, float* __restrict__ out,
                                                             int n, int nblk, float scale,
@@ -326,6 +331,7 @@ extern "C" int dmh_linattn_apply(const float* qkv, const float* ctx, float* out,
 
 extern "C" int dmh_attention(const float* qkv, float* out, int B, int n, float scale, const int32_t* rows, void* stream) {
   DMH_REQUIRE(qkv && out && B > 0 && n > 0, "dmh_attention: bad arguments");
+  // query and key tiles of 32 (no export; tests/test_gpu_attn_core.py runs n = 31 ... 33, 63 ... 65 and 1025 around them)
   const int qtiles = cdiv(n, 32);
   const int waves = B * 4 * qtiles;  // always a multiple of 4: one workgroup = the 4 heads' waves in flight
   hipLaunchKernelGGL(attention_kernel, dim3(waves / 4), dim3(256), 0, (hipStream_t)stream, qkv, out, n, qtiles, scale, rows);

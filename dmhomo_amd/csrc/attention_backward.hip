@@ -17,7 +17,7 @@
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-#define LAB_TILES 4  // 32-pixel tiles per wave
+#define LAB_TILES 4  // 32-pixel tiles per wave (no export; tests/test_gpu_attn_core.py runs n = 127 ... 129 around one block)
 
 namespace {
 // acc[row c][col pixel] = sum_k mat[c][k] * x[pixel][k]:  a16[s] = mat[c = i][k = 16*half + s], x16[s] = x[pixel i][16*half + s]
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void linattn_bwd_q_kernel(const float* __restr
 }
 
 // ---- A2: part[split][b][h][d][e] = sum over the split's pixels of x[n][d] * y[n][e]   (x, y: [B][n][128], channel h*32+.)
-#define LAB_NS 128
+#define LAB_NS 128  // pixels per split (restated in tests/attn_core_cases.py, see tests/test_attn_core_host.py)
 __global__ __launch_bounds__(256) void pixel_outer_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                           float* __restrict__ part, int n, int nsplit, int B) {
   const int b = blockIdx.x / nsplit, sp = blockIdx.x % nsplit;
@@ -196,6 +196,7 @@ __global__ __launch_bounds__(256) void colsum128_kernel(const float* __restrict_
   __shared__ float red[256 * 4];
   const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
   const int q = threadIdx.x & 31, pl = threadIdx.x >> 5;  // 32 channel quads x 8 pixel lanes
+  // chunks of 256 pixels (restated in tests/attn_core_cases.py, see tests/test_attn_core_host.py)
   const int p0 = ch * 256, p1 = min(p0 + 256, n);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int p = p0 + pl; p < p1; p += 8) {
@@ -253,6 +254,7 @@ __global__ void sum_slabs_kernel(const float* __restrict__ in, float* __restrict
 extern "C" int64_t dmh_linattn_bwd_workspace_floats(int B, int n) {
   if (!dmh_dims_ok({B}) || !dmh_dims_ok({n}, 1, 1 << 26)) return -1;
   const int ns = cdiv(n, LAB_NS), nc = cdiv(n, 256);
+  // (the five regions and their order are restated in tests/attn_core_cases.py, see tests/test_attn_core_host.py)
   return (int64_t)B * n * 128                 // qs
          + (int64_t)ns * B * 4 * 1024         // dctx partials
          + (int64_t)B * 4 * 1024              // dctx
