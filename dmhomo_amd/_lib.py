@@ -158,6 +158,19 @@ SIGNATURES = {
                                      C.c_void_p, c_i64, C.c_void_p]),
     'dmh_sampler_step_thr_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
                                          C.c_void_p, c_i64, C.c_void_p]),
+    'dmh_guidance_splits': (c_int, [c_int, c_i64]),
+    'dmh_guidance_factor': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, C.c_void_p, c_float, C.c_void_p, c_f32p, c_int, c_i64,
+                                    C.c_void_p]),
+    'dmh_guidance_factor_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, c_float, C.c_void_p, c_f32p, c_int, c_i64,
+                                        C.c_void_p]),
+    'dmh_sampler_threshold_gr': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_int,
+                                         c_i64, c_i64, c_float, C.c_void_p]),
+    'dmh_sampler_threshold_gr_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_int, c_i64,
+                                             c_i64, c_float, C.c_void_p]),
+    'dmh_sampler_step_gr': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                    c_i64, C.c_void_p, c_i64, C.c_void_p]),
+    'dmh_sampler_step_gr_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                        c_i64, C.c_void_p, c_i64, C.c_void_p]),
     'dmh_rng_indexed': (c_int, [c_f32p, c_int, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     'dmh_rng_keep_mask': (c_int, [C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_float, C.c_void_p]),
     'dmh_rows_lincomb': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, C.c_void_p]),

@@ -256,15 +256,23 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
-        'dynamic', the step's thresholds 'thr')."""
+        'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac')."""
         batch, device = shape[0], self.betas.device
         steps = self._ddim_steps(clip_denoised, cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
+        phi = self._rescale_phi(cond_scale)
         img = self.rng.randn(shape, device).contiguous()
+        ws = ops.guidance_workspace(img) if phi else None
         for time, step, draws in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
             noise = self.rng.randn(shape, device).contiguous() if draws else None
+            if phi:
+                img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
+                                                            trace is not None)
+                if trace is not None:
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, **extra})
+                continue
             if rank is None:
                 img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
                 thr = None
@@ -284,6 +292,23 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             return None
         return self._quantile_rank(float(self.dynamic_threshold_percentile), shape[1] * shape[2] * shape[3])
 
+    def _rescale_phi(self, cond_scale):
+        """phi where the loop rescales its guidance (guidance_rescale > 0 and a null pass to rescale against: cond_scale != 1),
+        else 0.: the calls as they were"""
+        phi = self._check_guidance_rescale()
+        return phi if cond_scale != 1 else 0.
+
+    def _rescaled_update(self, step, cond, null, computed, img, noise, hist, rank, phi, ws, want_x_start):
+        """the update of one eager step under guidance_rescale: the factor per row, the threshold of the rescaled blend where
+        the loop thresholds dynamically, the step -> (img, x_start or None, what the trace adds)"""
+        gfac = ops.guidance_factor(step, cond, null, phi, keep=computed, ws=ws)
+        thr = None
+        if rank is not None:
+            thr, _ = ops.sampler_threshold_gr(step, cond, null, img, gfac, *rank, keep=computed)
+        img, x_start = ops.sampler_step_gr(step, cond, null, img, noise, hist, thr, gfac, want_x_start=want_x_start,
+                                           keep=computed)
+        return img, x_start, {'gfac': gfac, **({} if thr is None else {'thr': thr})}
+
     def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """the loop of _ddim_sample with the multistep solver's update (ScheduleHost._dpmpp_steps; not in the reference): the
         network call — its class-dropout draw included — is the same, the update draws nothing and carries the previous step's
@@ -291,11 +316,19 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         batch, device = shape[0], self.betas.device
         steps = self._dpmpp_steps(clip_denoised, cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
+        phi = self._rescale_phi(cond_scale)
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
+        ws = ops.guidance_workspace(img) if phi else None
         for time, step, _ in steps:
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
+            if phi:
+                img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
+                                                            trace is not None)
+                if trace is not None:
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, **extra})
+                continue
             if rank is None:
                 img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
                 thr = None
@@ -342,16 +375,20 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times.
         With sampler = 'dpmpp_2m' the step is the network, dmh_sampler_step_ms_dev on a static history buffer and the seek:
         no randn launch is left in it.  With clip_mode = 'dynamic' the update is two calls, dmh_sampler_threshold_dev and
-        dmh_sampler_step_thr_dev, on a static scratch and a static threshold per row."""
+        dmh_sampler_step_thr_dev, on a static scratch and a static threshold per row.  With guidance_rescale (and a null pass)
+        the update starts with dmh_guidance_factor_dev on a static factor per row and its static workspace, and the threshold
+        and the step are the _gr entries."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
         rank = self._dynamic_rank(shape, clip)               # None: the static clamp
+        phi = self._rescale_phi(cond_scale)                  # 0.: no rescale
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
                bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
                self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key(), self.sampler,
-               self.clip_mode, None if rank is None else float(self.dynamic_threshold_percentile))
+               self.clip_mode, None if rank is None else float(self.dynamic_threshold_percentile),
+               float(self.guidance_rescale))
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -366,9 +403,19 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if rank is not None:                             # dynamic thresholding: scratch for the raw x_start, a threshold per row
                 st['x0_raw'] = torch.zeros(shape, device=device)
                 st['thr'] = torch.ones((shape[0],), device=device)
+            if phi:                                          # guidance rescale: a factor per row, the fp64 partial moments
+                st['gfac'] = torch.ones((shape[0],), device=device)
+                st['gws'] = ops.guidance_workspace(st['img'])
 
             def step(cond, null, computed, noise, out):      # the update of the entry at the cursor
                 hist = st['hist'] if solver else None
+                if phi:
+                    ops.guidance_factor_dev(st['cur'], cond, null, phi, keep=computed, ws=st['gws'], gfac=st['gfac'])
+                    if rank is not None:
+                        ops.sampler_threshold_gr_dev(st['cur'], cond, null, st['img'], st['gfac'], *rank, keep=computed,
+                                                     x0_raw=st['x0_raw'], thr=st['thr'])
+                    return ops.sampler_step_gr_dev(st['cur'], cond, null, st['img'], noise, hist,
+                                                   None if rank is None else st['thr'], st['gfac'], out=out, keep=computed)
                 if rank is not None:
                     ops.sampler_threshold_dev(st['cur'], cond, null, st['img'], *rank, keep=computed, x0_raw=st['x0_raw'],
                                               thr=st['thr'])

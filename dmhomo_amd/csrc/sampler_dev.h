@@ -1,4 +1,5 @@
-// The denoise step on one element, shared by the step kernels of sampler.hip and the thresholding kernels of threshold.hip.
+// The denoise step on one element, shared by the step kernels of sampler.hip, the thresholding kernels of threshold.hip and
+// the guidance-rescale kernels of guidance.hip.
 // Mirrors the reference's fp32 op order: a file that includes this sets `#pragma clang fp contract(off)` first.
 #pragma once
 #include "common.h"
@@ -19,6 +20,16 @@ __device__ __forceinline__ float guided_logit(const float* mc, const float* mn, 
   const float nl = mn[i];
   const float mo = (keep && !keep[i / per_row]) ? nl : mc[i];
   return nl + (mo - nl) * cond_scale;
+}
+
+// guidance rescale (guidance.hip): the blend of guided_logit on values already read — the same fp32 expression, so that the
+// row moments of dmh_guidance_factor are those of what the step kernels blend — and guided_logit times its row's factor
+// gfac[i / per_row]; a factor of 1.0f leaves guided_logit's bits
+__device__ __forceinline__ float guided_blend(float mo, float nl, float cond_scale) { return nl + (mo - nl) * cond_scale; }
+
+__device__ __forceinline__ float rescaled_guided_logit(const float* mc, const float* mn, const uint8_t* keep, int64_t i,
+                                                       int64_t per_row, float cond_scale, const float* gfac) {
+  return guided_logit(mc, mn, keep, i, per_row, cond_scale) * gfac[i / per_row];
 }
 
 // x_start before any clamp (CFG:614-628): what the clamp of denoise_step and the row quantile of dmh_sampler_threshold see

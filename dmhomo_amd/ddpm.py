@@ -246,6 +246,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             raise ValueError("clip_mode = 'dynamic' is not available in the unconditional class: its samples carry two flow "
                              "channels on another scale than the image channels (sample() maps them back by x 512), so one "
                              "quantile over a sample's channels means nothing here; use clip_mode = 'static'")
+        if self._check_guidance_rescale() != 0.:
+            raise ValueError('guidance_rescale is not available in the unconditional class: it has no classifier-free guidance '
+                             'to rescale; use guidance_rescale = 0')
         if self._check_sampler() == 'dpmpp_2m':              # (walks the time list whatever is_ddim_sampling says)
             return self.dpmpp_sample(shape)
         return self.ddim_sample(shape) if self.is_ddim_sampling else self.p_sample_loop(shape)

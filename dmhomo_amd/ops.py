@@ -597,6 +597,104 @@ def sampler_step_thr_dev(cur, model_cond, model_null, x, noise, hist, thr, out=N
     return img
 
 
+def guidance_splits(B, n):
+    """workgroups per row of the guidance factor's first pass (dmh_guidance_splits): a pure function of (B, n)"""
+    s = int(_lib.lib().dmh_guidance_splits(int(B), int(n)))
+    if s < 1:
+        raise ValueError(f'guidance_splits: B = {B} rows of n = {n} elements')
+    return s
+
+
+def guidance_workspace(x):
+    """the fp64 workspace dmh_guidance_factor[_dev] asks for with logits of x's shape (B, ...): 4 doubles per (row, split)"""
+    B = x.shape[0]
+    return torch.empty((4 * B * guidance_splits(B, x.numel() // B),), device=x.device, dtype=torch.float64)
+
+
+def _guidance_buffers(who, model_cond, model_null, ws, gfac):
+    if model_null is None or tuple(model_null.shape) != tuple(model_cond.shape):
+        raise ValueError(f'{who}: model_null {None if model_null is None else tuple(model_null.shape)} against model_cond '
+                         f'{tuple(model_cond.shape)} (the factor needs the null pass)')
+    B = model_cond.shape[0]
+    ws = guidance_workspace(model_cond) if ws is None else ws
+    gfac = _empty((B,), model_cond) if gfac is None else gfac
+    need = 4 * B * guidance_splits(B, model_cond.numel() // B)
+    if ws.numel() < need or tuple(gfac.shape) != (B,):
+        raise ValueError(f'{who}: ws of {ws.numel()} doubles ({need} needed) / gfac {tuple(gfac.shape)} for {B} rows')
+    return ws, gfac
+
+
+def guidance_factor(step, model_cond, model_null, phi, keep=None, ws=None, gfac=None):
+    """the guidance-rescale factor of one denoise step (dmh_guidance_factor): gfac[b] = 1 + phi * (std(cond[b]) / std(blend[b])
+    - 1) with blend = null + (cond - null) * step.cond_scale and ``keep`` as sampler_step; fp64 moments, bitwise repeatable.
+    ws: guidance_workspace(model_cond).  -> gfac (B,)"""
+    ws, gfac = _guidance_buffers('guidance_factor', model_cond, model_null, ws, gfac)
+    call('dmh_guidance_factor', C.byref(step), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), float(phi),
+         ptr(ws, torch.float64), ptr(gfac), model_cond.shape[0], model_cond.numel() // model_cond.shape[0])
+    return gfac
+
+
+def guidance_factor_dev(cur, model_cond, model_null, phi, keep=None, ws=None, gfac=None):
+    """guidance_factor with its DmhStep in device memory (``cur`` of step_table)"""
+    ws, gfac = _guidance_buffers('guidance_factor_dev', model_cond, model_null, ws, gfac)
+    call('dmh_guidance_factor_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), float(phi),
+         ptr(ws, torch.float64), ptr(gfac), model_cond.shape[0], model_cond.numel() // model_cond.shape[0])
+    return gfac
+
+
+def _gfac_shape(who, x, gfac):
+    if tuple(gfac.shape) != (x.shape[0],):
+        raise ValueError(f'{who}: gfac {tuple(gfac.shape)} for {x.shape[0]} rows')
+
+
+def sampler_threshold_gr(step, model_cond, model_null, x, gfac, k, frac, keep=None, x0_raw=None, thr=None):
+    """sampler_threshold on the rescaled blend (dmh_sampler_threshold_gr): gfac (B,) from guidance_factor.  -> (thr, x0_raw)"""
+    x0_raw, thr = _threshold_buffers('sampler_threshold_gr', x, x0_raw, thr)
+    _gfac_shape('sampler_threshold_gr', x, gfac)
+    call('dmh_sampler_threshold_gr', C.byref(step), ptr(model_cond), ptr(model_null), ptr(x), ptr(keep, torch.uint8), ptr(gfac),
+         ptr(x0_raw), ptr(thr), x.shape[0], x.numel() // x.shape[0], int(k), float(frac))
+    return thr, x0_raw
+
+
+def sampler_threshold_gr_dev(cur, model_cond, model_null, x, gfac, k, frac, keep=None, x0_raw=None, thr=None):
+    """sampler_threshold_gr with its DmhStep in device memory (``cur`` of step_table)"""
+    x0_raw, thr = _threshold_buffers('sampler_threshold_gr_dev', x, x0_raw, thr)
+    _gfac_shape('sampler_threshold_gr_dev', x, gfac)
+    call('dmh_sampler_threshold_gr_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(keep, torch.uint8),
+         ptr(gfac), ptr(x0_raw), ptr(thr), x.shape[0], x.numel() // x.shape[0], int(k), float(frac))
+    return thr, x0_raw
+
+
+def _step_gr_shapes(who, x, noise, hist, thr, gfac):
+    for t in (noise, hist):
+        if t is not None and tuple(t.shape) != tuple(x.shape):
+            raise ValueError(f'{who}: {tuple(t.shape)} against x {tuple(x.shape)}')
+    if thr is not None and tuple(thr.shape) != (x.shape[0],):
+        raise ValueError(f'{who}: thr {tuple(thr.shape)} for {x.shape[0]} rows')
+    _gfac_shape(who, x, gfac)
+
+
+def sampler_step_gr(step, model_cond, model_null, x, noise, hist, thr, gfac, out=None, want_x_start=False, keep=None):
+    """sampler_step / sampler_step_ms / sampler_step_thr on the rescaled blend (dmh_sampler_step_gr): the guided logits of row b
+    times gfac[b], the step behind them unchanged.  ``noise`` for a DDIM entry, ``hist`` for a multistep entry (the other
+    None); ``thr`` None: the static clamp, else the threshold per row.  out may be x (in place).  -> (img, x_start or None)"""
+    _step_gr_shapes('sampler_step_gr', x, noise, hist, thr, gfac)
+    img = torch.empty_like(x) if out is None else out
+    xs = torch.empty_like(x) if want_x_start else None
+    call('dmh_sampler_step_gr', C.byref(step), ptr(model_cond), ptr(model_null), ptr(x), ptr(noise), ptr(hist), ptr(thr),
+         ptr(gfac), ptr(img), ptr(xs), x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img, xs
+
+
+def sampler_step_gr_dev(cur, model_cond, model_null, x, noise, hist, thr, gfac, out=None, x_start=None, keep=None):
+    """sampler_step_gr with its DmhStep in device memory (``cur`` of step_table); out may be x (in place)."""
+    _step_gr_shapes('sampler_step_gr_dev', x, noise, hist, thr, gfac)
+    img = torch.empty_like(x) if out is None else out
+    call('dmh_sampler_step_gr_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(x), ptr(noise), ptr(hist),
+         ptr(thr), ptr(gfac), ptr(img), ptr(x_start), x.numel(), ptr(keep, torch.uint8), x.numel() // x.shape[0])
+    return img
+
+
 def rng_indexed(shape, sample_ids, state, kind=0):
     """one draw of the sample-indexed generator (dmh_rng_indexed): (B, *shape[1:]) fp32 whose row b is a pure function of
     (state[0] = seed, sample_ids[b], state[1] = draw index, element); the launch advances the draw index.

@@ -351,6 +351,23 @@ class ScheduleHost:
             raise ValueError(f'dynamic_threshold_percentile = {p!r}: a number in (0, 1]')
         return self.clip_mode
 
+    # OPT-IN, 0. by default (every existing result stays what it is).  phi in (0, 1]: rescaled classifier-free guidance (Lin et
+    # al. 2024, "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4; the reference has none) in the conditional
+    # class's sample(): per sample and step the guided blend null + (cond - null) * cond_scale is multiplied by g = 1 + phi *
+    # (std(cond) / std(blend) - 1), which brings it back towards the standard deviation of the conditional output — the remedy
+    # for the CAUSE of the saturation that clip_mode = 'dynamic' treats at x_start (a cosine schedule has zero terminal SNR, the
+    # regime that paper describes; its value is 0.7).  The factor comes from fp64 row moments (dmh_guidance_factor); a sample
+    # whose cond equals its null gets g == 1 exactly.  It takes effect only where the network returns a null pass (cond_scale
+    # != 1), with both samplers and both clip modes.  What it does to samples of trained weights has not been measured.  The
+    # unconditional class refuses it (ddpm.GaussianDiffusion.sample).
+    guidance_rescale = 0.
+
+    def _check_guidance_rescale(self):
+        phi = self.guidance_rescale
+        if isinstance(phi, bool) or not (isinstance(phi, (int, float)) and 0. <= phi <= 1.):
+            raise ValueError(f'guidance_rescale = {phi!r}: a number in [0, 1]')
+        return float(phi)
+
     @staticmethod
     def _quantile_rank(p, n):
         """percentile p in (0, 1] of n values -> (k, frac): rank = p * (n - 1) in double, k = floor(rank), frac = the fp32

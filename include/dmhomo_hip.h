@@ -365,6 +365,49 @@ int dmh_sampler_step_thr_dev(const DmhStep* cur_dev, const float* model_cond, co
                              const float* noise, float* hist, const float* thr, float* img_out, float* x_start, int64_t n,
                              const uint8_t* keep, int64_t per_row, void* stream);
 
+/* Guidance rescale of the guided blend (Lin et al. 2024, "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4;
+ * not in the reference).  Per row b of n values (one sample: n = C*H*W):
+ *   mo_c[i] = model_cond[i], or model_null[i] where keep[b] == 0     (the conditional logit as dmh_sampler_step reads it)
+ *   cfg[i]  = nl + (mo_c - nl) * cond_scale, nl = model_null[i]      (the fp32 expression of the guided blend, CFG:410)
+ *   ratio   = std(mo_c) / std(cfg) over the row (population variance; only the ratio is used), 1 where std(cfg) == 0 (n == 1,
+ *             constant rows)
+ *   g[b]    = 1 + phi * (ratio - 1), rounded to fp32 once
+ * and a step works on blend * g[b] instead of the blend.  A row whose cond equals its null bitwise gets g == 1.0f exactly (the
+ * dropped rows of the conditional pass; a product with 1.0f is exact); a NaN or an infinity in a row makes that row's g NaN,
+ * and no other row's.
+ *
+ * dmh_guidance_splits(B, n): the workgroups per row of the first pass, a pure function of (B, n); -1 for B < 1 or n outside
+ * [1, 2^31).
+ * dmh_guidance_factor[_dev]: gfac [B] <- g.  Only cond_scale is read from the DmhStep (by value, or from device memory as
+ * dmh_sampler_step_dev reads it).  model_null is required (without a null pass there is nothing to rescale), 0 <= phi <= 1.
+ * ws: workspace of the caller, 4 * B * dmh_guidance_splits(B, n) doubles.  Two launches: per (row, split) the fp64 mean and sum
+ * of squared deviations of mo_c and of cfg into ws, then one thread per row merges them in split order.  No floating-point
+ * atomics, no arrival counter: bitwise repeatable, and a row's g does not depend on the rows beside it.
+ * dmh_sampler_threshold_gr[_dev]: dmh_sampler_threshold[_dev] on the rescaled blend (gfac [B]): x0_raw = the raw x_start of
+ * blend * g[b], thr = max(1, its row quantile) through dmh_row_quantile_abs's selector.
+ * dmh_sampler_step_gr[_dev]: one entry for DDIM, last and multistep entries on the rescaled blend.  gfac [n / per_row] is
+ * required; noise, hist and thr are optional: noise and hist as dmh_sampler_step_thr's (they exclude each other; the
+ * host-struct form refuses a DDIM entry without noise, a multistep entry without hist and mode 2), thr == NULL is the static
+ * clamp of dmh_sampler_step, thr [n / per_row] the threshold of dmh_sampler_step_thr.  gfac == 1 gives the bits of
+ * dmh_sampler_step / dmh_sampler_step_ms / dmh_sampler_step_thr.  img_out may alias x. */
+int dmh_guidance_splits(int B, int64_t n);
+int dmh_guidance_factor(const DmhStep* s, const float* model_cond, const float* model_null, const uint8_t* keep, float phi,
+                        double* ws, float* gfac, int B, int64_t n, void* stream);
+int dmh_guidance_factor_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const uint8_t* keep,
+                            float phi, double* ws, float* gfac, int B, int64_t n, void* stream);
+int dmh_sampler_threshold_gr(const DmhStep* s, const float* model_cond, const float* model_null, const float* x,
+                             const uint8_t* keep, const float* gfac, float* x0_raw, float* thr, int B, int64_t n, int64_t k,
+                             float frac, void* stream);
+int dmh_sampler_threshold_gr_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const float* x,
+                                 const uint8_t* keep, const float* gfac, float* x0_raw, float* thr, int B, int64_t n,
+                                 int64_t k, float frac, void* stream);
+int dmh_sampler_step_gr(const DmhStep* s, const float* model_cond, const float* model_null, const float* x, const float* noise,
+                        float* hist, const float* thr, const float* gfac, float* img_out, float* x_start, int64_t n,
+                        const uint8_t* keep, int64_t per_row, void* stream);
+int dmh_sampler_step_gr_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const float* x,
+                            const float* noise, float* hist, const float* thr, const float* gfac, float* img_out,
+                            float* x_start, int64_t n, const uint8_t* keep, int64_t per_row, void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

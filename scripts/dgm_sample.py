@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -14,6 +14,8 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
   * --clip_mode dynamic replaces the clamp of every step's x_start to [-1, 1] by dynamic thresholding at the
     --dynamic_threshold_percentile-th percentile of each sample's |x_start| (an addition: the reference clamps); the default,
     static, is the reference's clamp;
+  * --guidance_rescale PHI in (0, 1] rescales every step's guided blend towards the standard deviation of its conditional
+    output (rescaled classifier-free guidance, Lin et al. 2024; an addition); the default, 0, is the reference's blend;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -63,6 +65,9 @@ parser.add_argument('--clip_mode', choices=('static', 'dynamic'), default='stati
                          "2022; not in the reference; ScheduleHost.clip_mode)")
 parser.add_argument('--dynamic_threshold_percentile', type=float, default=0.995,
                     help='the percentile of |x_start| per sample that --clip_mode dynamic clamps at, in (0, 1]')
+parser.add_argument('--guidance_rescale', type=float, default=0.,
+                    help='phi of rescaled classifier-free guidance in [0, 1] (Lin et al. 2024 use 0.7; not in the reference; '
+                         'ScheduleHost.guidance_rescale); 0: off')
 args = parser.parse_args()
 
 num_classes = 1
@@ -92,6 +97,7 @@ def main():
     sampler.hip_graph = True                               # one captured denoise step replayed s_step times
     sampler.sampler = args.sampler
     sampler.clip_mode, sampler.dynamic_threshold_percentile = args.clip_mode, args.dynamic_threshold_percentile
+    sampler.guidance_rescale = args.guidance_rescale
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
