@@ -5,7 +5,9 @@ missing or a symbol cannot be resolved, importing / calling fails loudly.
 Tensors cross the boundary as raw device pointers (``tensor.data_ptr()``) plus
 sizes; the HIP stream is torch's current stream.
 """
+import contextlib
 import ctypes as C
+import gc
 import os
 
 import torch
@@ -229,6 +231,25 @@ def lib():
 
 def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def graph_capture(graph, pool=None):
+    """``torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local')`` with Python's cyclic collector kept out of
+    the capture.  A dropped diffusion object or evicted capture is a reference cycle (entry -> step body -> entry) that
+    holds HIP graphs and their memory pool; only the collector frees it, and where it happened to run inside a capture the
+    graph and pool destructors called into HIP from the capturing thread, which a thread-local capture forbids: the process
+    aborted.  (torch.cuda.graph collected on entry until torch 2.9; it no longer does.)  So: collect first, then hold the
+    collector off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local'):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def call(name, *args):

@@ -7,7 +7,7 @@ import math
 import torch
 
 from . import ops
-from ._lib import DmhStep
+from ._lib import DmhStep, graph_capture
 from .schedule import ddim_pairs, make_buffers
 
 ModelPrediction = namedtuple('ModelPrediction', ['pred_noise', 'pred_x_start'])
@@ -441,10 +441,10 @@ class ScheduleHost:
                     last()
                 torch.cuda.current_stream().wait_stream(side)
                 g_mid = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_mid, capture_error_mode='thread_local'):
+                with graph_capture(g_mid):
                     mid()
                 g_last = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_last, pool=g_mid.pool(), capture_error_mode='thread_local'):
+                with graph_capture(g_last, pool=g_mid.pool()):
                     st['out'] = last()
             finally:
                 self.model.__dict__.pop('_ss_tab', None)

@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import ops
+from ._lib import graph_capture
 from .layout import ATTN_SCALE, HIDDEN, sinusoidal_freq, unet_layout
 
 
@@ -521,7 +522,7 @@ class TrainStep:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # thread_local: other threads of the process (e.g. the RCCL watchdog) may keep calling into HIP meanwhile
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                with graph_capture(g):
                     self.ut.repack()
                 self._repack_graph = g
             except Exception as e:                         # capture not available: stay on plain launches

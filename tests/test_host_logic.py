@@ -375,3 +375,50 @@ def test_runtime_switches_are_the_documented_ones():
         found |= set(re.findall(r'''['"](DMH_[A-Z0-9_]+)['"]''', open(path).read()))
     assert stamps_only in found
     assert found - {stamps_only} == documented, (sorted(found - documented), sorted(documented - found))
+
+
+def test_graph_capture_keeps_the_cyclic_collector_out(monkeypatch):
+    """_lib.graph_capture: a dead reference cycle (what a dropped diffusion object with captured steps is) is collected BEFORE
+    the capture begins, the collector is off for the capture's duration — a collection inside it ran HIP graph destructors on
+    the capturing thread and aborted the process — and back on afterwards, also when the body raises"""
+    import contextlib
+    import gc
+    import weakref
+    from dmhomo_amd import _lib
+
+    class Node:
+        pass
+
+    seen = {}
+
+    @contextlib.contextmanager
+    def fake_graph(graph, pool=None, capture_error_mode=None):
+        seen.update(graph=graph, pool=pool, mode=capture_error_mode, alive_at_entry=ref() is not None, gc_on=gc.isenabled())
+        yield
+
+    monkeypatch.setattr(torch.cuda, 'graph', fake_graph)
+    assert gc.isenabled()
+    gc.collect()
+    gc.disable()              # (no automatic collection between making the cycle and the call under test)
+    try:
+        a, b = Node(), Node()
+        a.other, b.other = b, a
+        ref = weakref.ref(a)
+        del a, b
+        assert ref() is not None
+    finally:
+        gc.enable()
+    with _lib.graph_capture('g', pool='p'):
+        assert not gc.isenabled()
+    assert seen == dict(graph='g', pool='p', mode='thread_local', alive_at_entry=False, gc_on=False) and gc.isenabled()
+    with pytest.raises(KeyError):
+        with _lib.graph_capture('g'):
+            raise KeyError('body')
+    assert gc.isenabled() and seen['pool'] is None
+    gc.disable()
+    try:
+        with _lib.graph_capture('g'):
+            pass
+        assert not gc.isenabled()      # a caller that had the collector off keeps it off
+    finally:
+        gc.enable()
