@@ -113,10 +113,13 @@ class Unet(nn.Module):
     cfg_mode = 'batched'
     stream_splits = 1      # 'streams' mode: row sub-batches per pass, each on its own stream
 
-    def _cond_null(self, x, time, classes, rgb_flow, mask):
+    def _cond_null(self, x, time, classes, rgb_flow, mask, gate=None):
         """the two passes of CFG:404,409: (cond logits, null logits, computed).  computed is None — every row of the cond
         logits was computed — or, with ``dedup_dropped_rows``, the (B,) uint8 class-keep mask: rows where it is 0 were left
-        UNWRITTEN in the cond logits and equal the null logits' rows (``ops.sampler_step(..., keep=computed)``)."""
+        UNWRITTEN in the cond logits and equal the null logits' rows (``ops.sampler_step(..., keep=computed)``).
+        gate: None, or the (cursor, guided) device tables of a replayed step under ``guidance_interval``: every pass then takes
+        a row list from ``ops.rows_gated`` — at an unguided entry all B conditional rows are computed and no null row; the caller
+        puts ``ops.guidance_gate`` behind the network."""
         B = x.shape[0]
         keep = self._keep_mask(B, self.cond_drop_prob, x.device)
         null = self._null_mask(B, x.device)
@@ -135,7 +138,7 @@ class Unet(nn.Module):
             null_out = torch.empty_like(cond_out)
             bounds = [(i * B) // nsub for i in range(nsub + 1)]
             si = 0
-            for k, dst, sub in ((keep, cond_out, dedup), (null, null_out, False)):
+            for k, dst, sub, null_side in ((keep, cond_out, dedup, False), (null, null_out, False, True)):
                 for lo, hi in zip(bounds[:-1], bounds[1:]):
                     st = self._side[si]
                     si += 1
@@ -144,13 +147,20 @@ class Unet(nn.Module):
                         kk = None if k is None else k[lo:hi].contiguous()
                         fs = None if first is None else (first[0][lo:hi], first[1][lo:hi])
                         # (the pass writes its rows of the result itself: the fused final projection's destination)
+                        if gate is not None:
+                            rows = ops.rows_gated(kk if sub else None, hi - lo, 0, *gate, null_side=null_side)
+                        else:
+                            rows = ops.rows_from_keep(kk) if sub else None
                         self._run(None, time[lo:hi], classes[lo:hi], None, None, [kk], x0=x0[lo:hi], first=fs, out=dst[lo:hi],
-                                  rows=ops.rows_from_keep(kk) if sub else None)
+                                  rows=rows)
             for st in self._side:
                 cur.wait_stream(st)
             return cond_out, null_out, (keep if dedup else None)
-        both = self._run(x, time, classes, rgb_flow, mask, [keep, null],
-                         rows=ops.rows_from_keep(keep, extra=B) if dedup else None)
+        if gate is not None:
+            rows = ops.rows_gated(keep if dedup else None, B, B, *gate)
+        else:
+            rows = ops.rows_from_keep(keep, extra=B) if dedup else None
+        both = self._run(x, time, classes, rgb_flow, mask, [keep, null], rows=rows)
         return both[:B], both[B:], (keep if dedup else None)
 
     # OPT-IN, off by default (bench.py's headline keeps it off and reports it under "variants").  The reference's conditional
@@ -202,11 +212,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def rng(self, value):
         self.model.rng = value
 
-    def _network(self, x, t, classes, rgb_flow, mask, cond_scale):
-        """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null"""
+    def _network(self, x, t, classes, rgb_flow, mask, cond_scale, gate=None):
+        """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null (``gate`` too)"""
         if cond_scale == 1:
             return self.model.forward(x, t, classes, rgb_flow, mask), None, None
-        return self.model._cond_null(x, t, classes, rgb_flow, mask)
+        return self.model._cond_null(x, t, classes, rgb_flow, mask, gate)
 
     def model_predictions(self, x, t, classes, rgb_flow, mask, cond_scale=3., clip_x_start=False):
         """CFG:610-630.  One timestep for the whole batch (what the samplers pass): blend, objective branch and clamp in
@@ -256,22 +266,25 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
-        'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac')."""
+        'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac' at the guided entries; 'guided': whether
+        the entry ran with the null pass, False only under guidance_interval)."""
         batch, device = shape[0], self.betas.device
         steps = self._ddim_steps(clip_denoised, cond_scale)
+        guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
         img = self.rng.randn(shape, device).contiguous()
         ws = ops.guidance_workspace(img) if phi else None
-        for time, step, draws in steps:
+        for k, (time, step, draws) in enumerate(steps):
+            on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
+            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
             noise = self.rng.randn(shape, device).contiguous() if draws else None
-            if phi:
+            if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
                                                             trace is not None)
                 if trace is not None:
-                    trace.append({'time': time, 'x_start': x_start, 'img': img, **extra})
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra})
                 continue
             if rank is None:
                 img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
@@ -281,7 +294,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start = ops.sampler_step_thr(step, cond, null, img, noise, None, thr, want_x_start=trace is not None,
                                                     keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img, **({} if thr is None else {'thr': thr})})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr})})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -315,19 +328,21 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         x_start in ``hist``.  ``trace`` as _ddim_sample."""
         batch, device = shape[0], self.betas.device
         steps = self._dpmpp_steps(clip_denoised, cond_scale)
+        guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
-        for time, step, _ in steps:
+        for k, (time, step, _) in enumerate(steps):
+            on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale)
-            if phi:
+            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
                                                             trace is not None)
                 if trace is not None:
-                    trace.append({'time': time, 'x_start': x_start, 'img': img, **extra})
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra})
                 continue
             if rank is None:
                 img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
@@ -337,7 +352,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start = ops.sampler_step_thr(step, cond, null, img, None, hist, thr, want_x_start=trace is not None,
                                                     keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img, **({} if thr is None else {'thr': thr})})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr})})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -377,18 +392,24 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         no randn launch is left in it.  With clip_mode = 'dynamic' the update is two calls, dmh_sampler_threshold_dev and
         dmh_sampler_step_thr_dev, on a static scratch and a static threshold per row.  With guidance_rescale (and a null pass)
         the update starts with dmh_guidance_factor_dev on a static factor per row and its static workspace, and the threshold
-        and the step are the _gr entries."""
+        and the step are the _gr entries.  With guidance_interval (and a null pass) the same ONE step serves guided and unguided
+        entries: a static flag per entry, 'guided', written by fill on every call, is read at the cursor by dmh_rows_gated (the row
+        lists of the network: no null rows at an unguided entry) and by dmh_guidance_gate behind the network (null <- cond there),
+        and every launch behind the gate is the one it was."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
         rank = self._dynamic_rank(shape, clip)               # None: the static clamp
         phi = self._rescale_phi(cond_scale)                  # 0.: no rescale
+        gated = self._check_guidance_interval() is not None and cond_scale != 1      # (the interval's VALUE is not baked in)
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
                bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
                self.num_timesteps, self.objective, float(self.ddim_sampling_eta), clip, self.rng.graph_key(), self.sampler,
                self.clip_mode, None if rank is None else float(self.dynamic_threshold_percentile),
                float(self.guidance_rescale))
+        if gated:
+            key = key + ('guidance_interval',)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -406,6 +427,16 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if phi:                                          # guidance rescale: a factor per row, the fp64 partial moments
                 st['gfac'] = torch.ones((shape[0],), device=device)
                 st['gws'] = ops.guidance_workspace(st['img'])
+            if gated:                                        # guidance interval: a flag per entry (all guided until fill writes it)
+                st['guided'] = torch.ones((len(times),), device=device, dtype=torch.uint8)
+            gate = (st['cursor'], st['guided']) if gated else None
+
+            def network():                                   # -> the logits the update reads
+                if gate is None:
+                    return self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
+                cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale, gate)
+                ops.guidance_gate(*gate, cond, null)         # an unguided entry: null <- cond, the update below is the unguided one
+                return cond, null, computed
 
             def step(cond, null, computed, noise, out):      # the update of the entry at the cursor
                 hist = st['hist'] if solver else None
@@ -426,12 +457,12 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 return ops.sampler_step_dev(st['cur'], cond, null, st['img'], noise, out=out, keep=computed)
 
             def mid():                                       # one denoise step of CFG:684-707, in place on st['img']
-                logits = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
+                logits = network()
                 step(*logits, None if solver else self.rng.randn(shape, device).contiguous(), st['img'])
                 ops.sampler_seek(st['cursor'], -1, st['table'], st['times'], st['cur'], st['tcond'])
 
             def last():                                      # CFG:693-695 + unnormalize, CFG:709
-                logits = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
+                logits = network()
                 return ops.affine(step(*logits, None, None), 0.5, 0.5)
             return mid, last
 
@@ -440,6 +471,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 dst.copy_(src)
             ops.affine(st['ins'][1], 2., -1., out=st['rf'])  # normalize_to_neg_one_to_one, CFG:716
             st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
+            if gated:
+                flags = self._guided_entries(self._graph_tables(cond_scale, clip)[1], cond_scale)
+                st['guided'].copy_(torch.tensor(flags, dtype=torch.uint8))
         img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip), buffers, fill)
         return img, mask, flow
 

@@ -382,3 +382,88 @@ extern "C" int dmh_sampler_step_gr_dev(const DmhStep* cur_dev, const float* mode
   DMH_CHECK_LAUNCH("dmh_sampler_step_gr_dev");
   return DMH_OK;
 }
+
+// ---- Guidance interval (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and Distribution
+// Quality in Diffusion Models"; not in the reference): ONE captured denoise step serves guided and unguided entries.  The host
+// writes guided [S] (uint8, one flag per entry of the step table) and the step cursor of dmh_sampler_seek selects the entry;
+// both new kernels read the flag with one uniform load.  A cursor outside [0, S) counts as guided: the full work, and no read
+// outside the table.
+__device__ __forceinline__ bool entry_guided(const int32_t* cursor, const uint8_t* guided, int S) {
+  const int c = *cursor;
+  return c < 0 || c >= S || guided[c] != 0;
+}
+
+// dmh_rows_from_keep with the flag in front of it (one wave, the same ballot compaction, ascending).  Guided: the conditional
+// side lists the rows with keep != 0 (all B without keep), the null-only side all B, both followed by B .. B + extra - 1.
+// Unguided: the conditional side lists ALL B rows (a dropped row has no null row to borrow from) and no extras, the null-only
+// side nothing.  Slots behind 1 + n stay unwritten.
+__global__ __launch_bounds__(64) void rows_gated_kernel(const uint8_t* __restrict__ keep, int B, int extra,
+                                                        const int32_t* __restrict__ cursor,
+                                                        const uint8_t* __restrict__ guided, int S, int null_side,
+                                                        int32_t* __restrict__ rows) {
+  const bool on = entry_guided(cursor, guided, S);
+  if (!on && null_side) {
+    if (threadIdx.x == 0) rows[0] = 0;
+    return;
+  }
+  const bool masked = on && !null_side && keep;
+  int n = 0;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int b = b0 + (int)threadIdx.x;
+    const bool k = b < B && (!masked || keep[b] != 0);
+    const unsigned long long m = __ballot(k);
+    if (k) rows[1 + n + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = b;
+    n += __popcll(m);
+  }
+  const int ex = on ? extra : 0;
+  for (int j = threadIdx.x; j < ex; j += 64) rows[1 + n + j] = B + j;
+  if (threadIdx.x == 0) rows[0] = n + ex;
+}
+
+extern "C" int dmh_rows_gated(const uint8_t* keep, int B, int extra, const int32_t* cursor, const uint8_t* guided, int S,
+                              int null_side, int32_t* rows, void* stream) {
+  DMH_REQUIRE(cursor && guided && rows, "dmh_rows_gated: null pointer");
+  DMH_REQUIRE(B > 0 && extra >= 0 && S > 0 && (int64_t)B + extra < ((int64_t)1 << 31),
+              "dmh_rows_gated: B=%d rows, extra=%d, S=%d entries (B >= 1, extra >= 0, S >= 1)", B, extra, S);
+  DMH_REQUIRE(null_side == 0 || null_side == 1, "dmh_rows_gated: null_side=%d (0 conditional side, 1 null-only side)", null_side);
+  hipLaunchKernelGGL(rows_gated_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, keep, B, extra, cursor, guided, S, null_side,
+                     rows);
+  DMH_CHECK_LAUNCH("dmh_rows_gated");
+  return DMH_OK;
+}
+
+// The gate behind the network.  Guided entry: every workgroup returns before it touches cond or null.  Unguided entry: null <-
+// cond, bit for bit (32-bit words, no floating-point instruction sees them).  Where the two pointers meet 16 B boundaries
+// together: a scalar head up to the boundary, 16 B vectors, a scalar tail; else words.
+__global__ __launch_bounds__(256) void guidance_gate_kernel(const int32_t* __restrict__ cursor, const uint8_t* __restrict__ guided,
+                                                            int S, const uint32_t* __restrict__ cond, uint32_t* __restrict__ null,
+                                                            int64_t n) {
+  if (entry_guided(cursor, guided, S)) return;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  if ((((uintptr_t)cond ^ (uintptr_t)null) & 15u) != 0) {
+    for (int64_t i = tid; i < n; i += stride) null[i] = cond[i];
+    return;
+  }
+  int64_t head = (int64_t)(((16u - (unsigned)((uintptr_t)null & 15u)) & 15u) >> 2);
+  head = head < n ? head : n;
+  const int64_t nv = (n - head) >> 2, t0 = head + nv * 4;
+  if (tid < head) null[tid] = cond[tid];
+  const uint4* vc = reinterpret_cast<const uint4*>(cond + head);
+  uint4* vn = reinterpret_cast<uint4*>(null + head);
+  for (int64_t i = tid; i < nv; i += stride) vn[i] = vc[i];
+  if (tid < n - t0) null[t0 + tid] = cond[t0 + tid];
+}
+
+extern "C" int dmh_guidance_gate(const int32_t* cursor, const uint8_t* guided, int S, const float* cond, float* null, int64_t n,
+                                 void* stream) {
+  DMH_REQUIRE(cursor && guided && cond && null, "dmh_guidance_gate: null pointer");
+  DMH_REQUIRE(n > 0 && S > 0, "dmh_guidance_gate: n=%lld elements, S=%d entries (n >= 1, S >= 1)", (long long)n, S);
+  DMH_REQUIRE((((uintptr_t)cond | (uintptr_t)null) & 3u) == 0, "dmh_guidance_gate: cond / null are not 4-byte aligned");
+  DMH_REQUIRE(n < ((int64_t)1 << 40), "dmh_guidance_gate: n=%lld elements (limit 2^40)", (long long)n);
+  const uintptr_t pc = (uintptr_t)cond, pn = (uintptr_t)null, bytes = (uintptr_t)n * 4u;
+  DMH_REQUIRE(pc + bytes <= pn || pn + bytes <= pc, "dmh_guidance_gate: cond and null overlap");
+  hipLaunchKernelGGL(guidance_gate_kernel, dim3(grid_for(cdiv64(n, 4))), dim3(256), 0, (hipStream_t)stream, cursor, guided, S,
+                     (const uint32_t*)cond, (uint32_t*)null, n);
+  DMH_CHECK_LAUNCH("dmh_guidance_gate");
+  return DMH_OK;
+}

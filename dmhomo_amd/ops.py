@@ -695,6 +695,40 @@ def sampler_step_gr_dev(cur, model_cond, model_null, x, noise, hist, thr, gfac, 
     return img
 
 
+def _interval_tables(who, cursor, guided):
+    if tuple(cursor.shape) != (1,) or guided.dim() != 1 or guided.shape[0] < 1:
+        raise ValueError(f'{who}: cursor {tuple(cursor.shape)} / guided {tuple(guided.shape)} (one cursor, one flag per entry)')
+    return ptr(cursor, torch.int32), ptr(guided, torch.uint8), guided.shape[0]
+
+
+def rows_gated(keep, B, extra, cursor, guided, null_side=False, rows=None):
+    """rows_from_keep behind the guidance interval's flag guided[cursor] (dmh_rows_gated; cursor, guided: device tensors of a
+    replayed loop): int32 (1 + B + extra,).  A guided entry: the rows with keep != 0 (all B where keep is None, or on the
+    null-only side), then B .. B + extra - 1; an unguided entry: all B rows and no extras, or — null_side — none.
+    rows: the buffer to write (else a new one); the words behind rows[0 .. n] are left as they are."""
+    B, extra = int(B), int(extra)
+    if keep is not None and tuple(keep.shape) != (B,):
+        raise ValueError(f'rows_gated: keep {tuple(keep.shape)} for {B} rows')
+    pc, pg, S = _interval_tables('rows_gated', cursor, guided)
+    if rows is None:
+        rows = torch.empty((1 + max(B, 0) + max(extra, 0),), device=guided.device, dtype=torch.int32)
+    elif tuple(rows.shape) != (1 + B + extra,):
+        raise ValueError(f'rows_gated: rows {tuple(rows.shape)} for {B} rows and {extra} extras')
+    call('dmh_rows_gated', ptr(keep, torch.uint8), B, extra, pc, pg, S, int(bool(null_side)), ptr(rows, torch.int32))
+    return rows
+
+
+def guidance_gate(cursor, guided, cond, null):
+    """the gate behind the network of a replayed step under a guidance interval (dmh_guidance_gate): at an unguided entry
+    (guided[cursor] == 0) null <- cond bit for bit, so that every step kernel behind it does the unguided step; at a guided
+    entry nothing is touched.  -> null"""
+    if tuple(null.shape) != tuple(cond.shape):
+        raise ValueError(f'guidance_gate: null {tuple(null.shape)} against cond {tuple(cond.shape)}')
+    pc, pg, S = _interval_tables('guidance_gate', cursor, guided)
+    call('dmh_guidance_gate', pc, pg, S, ptr(cond), ptr(null), cond.numel())
+    return null
+
+
 def rng_indexed(shape, sample_ids, state, kind=0):
     """one draw of the sample-indexed generator (dmh_rng_indexed): (B, *shape[1:]) fp32 whose row b is a pure function of
     (state[0] = seed, sample_ids[b], state[1] = draw index, element); the launch advances the draw index.

@@ -368,6 +368,39 @@ class ScheduleHost:
             raise ValueError(f'guidance_rescale = {phi!r}: a number in [0, 1]')
         return float(phi)
 
+    # OPT-IN, None by default (every existing result, launch and graph key stays what it is).  (lo, hi) with 0 <= lo <= hi <= 1:
+    # limited-interval guidance (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and
+    # Distribution Quality in Diffusion Models"; the reference has none) in the conditional class's sample(): the entry of the
+    # sampling loop at timestep t is guided iff lo <= u <= hi, u = t / (num_timesteps - 1) in float64 (u = 1: pure noise).  A guided
+    # entry is what every entry is without the switch; an unguided one is the same entry at cond_scale == 1: the conditional pass
+    # alone (class-dropout draw included, so the generator is consumed identically), no blend, no guidance_rescale; clip_mode and
+    # the solver update are unchanged.  The null pass of an unguided entry is not computed: B UNet rows instead of 2B.  The
+    # replayed loop keeps its ONE captured step: a per-entry flag table next to the step table gates the row lists of the network
+    # (dmh_rows_gated) and copies cond over null behind it (dmh_guidance_gate), so changing the interval never captures again.
+    # With cond_scale == 1 it has no effect.  (The paper states its bounds in sigma; with sigma(t) = sqrt(1 / alphas_cumprod[t] -
+    # 1), u = the t whose sigma meets the bound, over num_timesteps - 1.)  What it does to samples of trained weights has not been
+    # measured.  The unconditional class refuses it (ddpm.GaussianDiffusion.sample).
+    guidance_interval = None
+
+    def _check_guidance_interval(self):
+        gi = self.guidance_interval
+        if gi is None:
+            return None
+        ok = isinstance(gi, (tuple, list)) and len(gi) == 2 and \
+            all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in gi)
+        if not (ok and 0. <= gi[0] <= gi[1] <= 1.):
+            raise ValueError(f'guidance_interval = {gi!r}: None, or a pair (lo, hi) of numbers with 0 <= lo <= hi <= 1')
+        return float(gi[0]), float(gi[1])
+
+    def _guided_entries(self, times, cond_scale):
+        """which entries of a sampling loop over ``times`` are guided under guidance_interval: a list of bools, or None where
+        the switch does nothing (no interval, or cond_scale == 1: no null pass to leave out) — the loops as they were"""
+        gi = self._check_guidance_interval()
+        if gi is None or cond_scale == 1:
+            return None
+        span = float(max(self.num_timesteps - 1, 1))
+        return [gi[0] <= float(t) / span <= gi[1] for t in times]
+
     @staticmethod
     def _quantile_rank(p, n):
         """percentile p in (0, 1] of n values -> (k, frac): rank = p * (n - 1) in double, k = floor(rank), frac = the fp32

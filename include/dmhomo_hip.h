@@ -408,6 +408,36 @@ int dmh_sampler_step_gr_dev(const DmhStep* cur_dev, const float* model_cond, con
                             const float* noise, float* hist, const float* thr, const float* gfac, float* img_out,
                             float* x_start, int64_t n, const uint8_t* keep, int64_t per_row, void* stream);
 
+/* Guidance interval (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and Distribution
+ * Quality in Diffusion Models"; not in the reference): classifier-free guidance on a middle part of the sampling loop only.
+ * An UNGUIDED entry is the entry at cond_scale == 1: the conditional pass alone, no blend.  In the replayed loop ONE captured
+ * step serves both kinds: guided [S] (uint8, device; one flag per entry of the step table, written by the host in front of
+ * every replay) is indexed by the step cursor of dmh_sampler_seek; both entry points read guided[*cursor] with one uniform
+ * load.  A cursor outside [0, S) cannot be refused at launch (device data) and counts as a guided entry.
+ *
+ * dmh_rows_gated: dmh_rows_from_keep behind that flag — rows in the format of "Row subsets", int32 [1 + B + extra], ascending,
+ * the slots behind 1 + n left unwritten.  keep: uint8 [B] or NULL (every row kept).
+ *   null_side == 0 (the conditional pass, or both passes in one 2B-row launch with extra = B):
+ *     guided entry    the slots b < B with keep[b] != 0 (all B where keep == NULL), then B .. B+extra-1
+ *     unguided entry  ALL B slots and no extras: a dropped row has no null row to borrow from, so it is computed, under the
+ *                     null embedding its keep bit already selects
+ *   null_side == 1 (a null-only pass; keep is not read):
+ *     guided entry    all B slots, then B .. B+extra-1;   unguided entry  n = 0
+ * One workgroup.
+ *
+ * dmh_guidance_gate: behind the network.  Guided entry: returns before touching cond or null.  Unguided entry: null[0 .. n)
+ * <- cond[0 .. n), bit for bit (NaN payloads and the sign of zero included; cond is never written), in 16-byte vectors where
+ * cond and null meet 16-byte boundaries together, with a scalar head and tail, in 4-byte words otherwise.  cond and null must
+ * not overlap.  Behind it every step kernel above does the unguided step unchanged: null + (cond - null) * s is cond where
+ * null == cond, dmh_guidance_factor answers exactly 1, rows with keep == 0 read a null row that holds their own conditional
+ * logits.  One difference to a call with model_null == NULL remains: the blend turns a logit of -0.0 into +0.0 (and an
+ * infinite one into NaN), where the call without a null pass hands it on; equal values otherwise, torch.equal does not see
+ * the zero. */
+int dmh_rows_gated(const uint8_t* keep, int B, int extra, const int32_t* cursor, const uint8_t* guided, int S, int null_side,
+                   int32_t* rows, void* stream);
+int dmh_guidance_gate(const int32_t* cursor, const uint8_t* guided, int S, const float* cond, float* null, int64_t n,
+                      void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -16,6 +16,9 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     static, is the reference's clamp;
   * --guidance_rescale PHI in (0, 1] rescales every step's guided blend towards the standard deviation of its conditional
     output (rescaled classifier-free guidance, Lin et al. 2024; an addition); the default, 0, is the reference's blend;
+  * --guidance_interval LO HI applies the guidance only at the entries whose normalised time t / (T - 1) lies in [LO, HI]; the
+    others run the conditional pass alone, at half the UNet rows (limited-interval guidance, Kynkaanniemi et al. 2024; an
+    addition); the default, off, guides every entry as the reference does;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -68,6 +71,9 @@ parser.add_argument('--dynamic_threshold_percentile', type=float, default=0.995,
 parser.add_argument('--guidance_rescale', type=float, default=0.,
                     help='phi of rescaled classifier-free guidance in [0, 1] (Lin et al. 2024 use 0.7; not in the reference; '
                          'ScheduleHost.guidance_rescale); 0: off')
+parser.add_argument('--guidance_interval', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='guide only where LO <= t / (T - 1) <= HI, 0 <= LO <= HI <= 1 (Kynkaanniemi et al. 2024; not in the '
+                         'reference; ScheduleHost.guidance_interval); default: every entry')
 args = parser.parse_args()
 
 num_classes = 1
@@ -98,6 +104,7 @@ def main():
     sampler.sampler = args.sampler
     sampler.clip_mode, sampler.dynamic_threshold_percentile = args.clip_mode, args.dynamic_threshold_percentile
     sampler.guidance_rescale = args.guidance_rescale
+    sampler.guidance_interval = None if args.guidance_interval is None else tuple(args.guidance_interval)
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
