@@ -175,6 +175,12 @@ SIGNATURES = {
                                         c_i64, C.c_void_p, c_i64, C.c_void_p]),
     'dmh_rows_gated': (c_int, [C.c_void_p, c_int, c_int, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p, C.c_void_p]),
     'dmh_guidance_gate': (c_int, [C.c_void_p, C.c_void_p, c_int, c_f32p, c_f32p, c_i64, C.c_void_p]),
+    'dmh_apg_splits': (c_int, [c_int, c_i64]),
+    'dmh_apg_coef': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, C.c_void_p, c_float, c_float, c_float, c_f32p, C.c_void_p, c_f32p,
+                             c_int, c_i64, C.c_void_p]),
+    'dmh_apg_coef_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, c_float, c_float, c_float, c_f32p, C.c_void_p, c_f32p,
+                                 c_int, c_i64, C.c_void_p]),
+    'dmh_apg_apply': (c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_int, c_i64, C.c_void_p]),
     'dmh_rng_indexed': (c_int, [c_f32p, c_int, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     'dmh_rng_keep_mask': (c_int, [C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_float, C.c_void_p]),
     'dmh_rows_lincomb': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, C.c_void_p]),

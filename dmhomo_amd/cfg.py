@@ -212,6 +212,65 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def rng(self, value):
         self.model.rng = value
 
+    # OPT-IN, None by default (every existing result, launch and graph key stays what it is).  apg_eta in [0, 1]: adaptive projected
+    # guidance (Sadat, Hilliges, Weber 2024, "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion Models",
+    # Algorithm 1; the reference has none) in sample(): per sample and step the update d = cond - null is split into its parts
+    # parallel and orthogonal to the conditional logits and the guided logits are cond + (cond_scale - 1) * s * (d_orth + apg_eta *
+    # d_par) — the paper attributes the saturation at high scales to the parallel part; 0 drops it, 1 keeps it (the usual blend in
+    # exact arithmetic, not bit for bit: None is "off").  apg_norm_threshold > 0 caps the update's norm per sample, s = min(1,
+    # threshold / |d|); apg_momentum in (-1, 1) replaces d by the running average d + momentum * (the previous step's average), zero
+    # at the start of every loop (the paper's values at cond_scale 10-15 are eta 0, threshold 2.5-15 at its latent sizes, momentum
+    # -0.5; the norm grows with sqrt(C * H * W)).  The definition is in include/dmhomo_hip.h; the coefficients come from fp64 row
+    # sums (dmh_apg_coef), the guided logits (dmh_apg_apply) go through the existing step and threshold kernels as a conditional
+    # output without a null pass, so both samplers and both clip modes take it.  It acts only where the network returns a null
+    # pass (cond_scale != 1).  Refused together with guidance_rescale > 0 (the paper offers APG in its place) and with
+    # guidance_interval (the running average across unguided entries has no definition yet).  model_predictions and
+    # forward_with_cond_scale do not know it.  What it does to samples of trained weights has not been measured.
+    apg_eta = None
+    apg_norm_threshold = 0.
+    apg_momentum = 0.
+
+    def _check_apg(self):
+        """-> None (off), or (eta, norm threshold, momentum) as floats"""
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        eta, rho, beta = self.apg_eta, self.apg_norm_threshold, self.apg_momentum
+        if eta is not None and not (num(eta) and 0. <= eta <= 1.):
+            raise ValueError(f'apg_eta = {eta!r}: None (off), or a number in [0, 1]')
+        if not (num(rho) and 0. <= rho < float('inf')):
+            raise ValueError(f'apg_norm_threshold = {rho!r}: a finite number >= 0 (0: no threshold)')
+        if not (num(beta) and -1. < beta < 1.):
+            raise ValueError(f'apg_momentum = {beta!r}: a number in (-1, 1)')
+        if eta is None:
+            return None
+        if self._check_guidance_rescale() > 0.:
+            raise ValueError(f'apg_eta = {eta!r} together with guidance_rescale = {self.guidance_rescale!r}: adaptive projected '
+                             f'guidance stands in place of the rescale, the two are not combined')
+        if self._check_guidance_interval() is not None:
+            raise ValueError(f'apg_eta = {eta!r} together with guidance_interval = {self.guidance_interval!r}: the running average '
+                             f'across unguided entries is not defined')
+        return float(eta), float(rho), float(beta)
+
+    def _apg_on(self, cond_scale):
+        """(eta, rho, beta) where the loop projects its guidance (apg_eta set and a null pass to project against: cond_scale !=
+        1), else None: the calls as they were"""
+        apg = self._check_apg()
+        return apg if cond_scale != 1 else None
+
+    @staticmethod
+    def _apg_state(img, apg):
+        """the buffers one eager loop keeps: the fp64 workspace, the guided logits and — with momentum — the running average,
+        zero at the start of the loop"""
+        return {'ws': ops.apg_workspace(img), 'guided': torch.empty_like(img),
+                'run': torch.zeros_like(img) if apg[2] != 0. else None}
+
+    @staticmethod
+    def _apg_logits(step, cond, null, computed, apg, ast):
+        """one eager step's guided logits: the coefficients, then the apply -> (guided, coef (B, 2)); the update behind it takes
+        (guided, None, keep=None)"""
+        eta, rho, beta = apg
+        coef = ops.apg_coef(step, cond, null, eta, rho, beta, keep=computed, run=ast['run'], ws=ast['ws'])
+        return ops.apg_apply(cond, null, coef, keep=computed, run=ast['run'], out=ast['guided']), coef
+
     def _network(self, x, t, classes, rgb_flow, mask, cond_scale, gate=None):
         """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null (``gate`` too)"""
         if cond_scale == 1:
@@ -267,19 +326,25 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
         'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac' at the guided entries; 'guided': whether
-        the entry ran with the null pass, False only under guidance_interval)."""
+        the entry ran with the null pass, False only under guidance_interval; with apg_eta, the step's (A, Cc) per row, 'apg' (B, 2))."""
         batch, device = shape[0], self.betas.device
         steps = self._ddim_steps(clip_denoised, cond_scale)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
+        apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
         img = self.rng.randn(shape, device).contiguous()
         ws = ops.guidance_workspace(img) if phi else None
+        ast = self._apg_state(img, apg) if apg else None
         for k, (time, step, draws) in enumerate(steps):
             on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
             noise = self.rng.randn(shape, device).contiguous() if draws else None
+            more = {}
+            if apg:                                          # the projected logits, then the update without a null pass
+                cond, coef = self._apg_logits(step, cond, null, computed, apg, ast)
+                null, computed, more = None, None, {'apg': coef}
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
                                                             trace is not None)
@@ -294,7 +359,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start = ops.sampler_step_thr(step, cond, null, img, noise, None, thr, want_x_start=trace is not None,
                                                     keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr})})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
+                              **more})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -331,13 +397,19 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
+        apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
+        ast = self._apg_state(img, apg) if apg else None
         for k, (time, step, _) in enumerate(steps):
             on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
             cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            more = {}
+            if apg:                                          # the projected logits, then the update without a null pass
+                cond, coef = self._apg_logits(step, cond, null, computed, apg, ast)
+                null, computed, more = None, None, {'apg': coef}
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
                                                             trace is not None)
@@ -352,7 +424,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start = ops.sampler_step_thr(step, cond, null, img, None, hist, thr, want_x_start=trace is not None,
                                                     keep=computed)
             if trace is not None:
-                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr})})
+                trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
+                              **more})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -395,13 +468,16 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         and the step are the _gr entries.  With guidance_interval (and a null pass) the same ONE step serves guided and unguided
         entries: a static flag per entry, 'guided', written by fill on every call, is read at the cursor by dmh_rows_gated (the row
         lists of the network: no null rows at an unguided entry) and by dmh_guidance_gate behind the network (null <- cond there),
-        and every launch behind the gate is the one it was."""
+        and every launch behind the gate is the one it was.  With apg_eta (and a null pass) the update starts with dmh_apg_coef_dev and
+        dmh_apg_apply on static buffers (the guided logits, the coefficients, the fp64 workspace and, with momentum, the running
+        average, which fill zeroes on every call), and the launches behind them are those of cond_scale == 1 on the guided logits."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
         rank = self._dynamic_rank(shape, clip)               # None: the static clamp
         phi = self._rescale_phi(cond_scale)                  # 0.: no rescale
         gated = self._check_guidance_interval() is not None and cond_scale != 1      # (the interval's VALUE is not baked in)
+        apg = self._apg_on(cond_scale)                       # None: off.  (It refuses phi and an interval beside it.)
         # everything besides weights, schedule and device that is baked into the captured launches or the step tables
         key = (tuple(shape), tuple(rgb_flow.shape), float(cond_scale), m.cfg_mode, int(m.stream_splits),
                bool(m.dedup_dropped_rows), float(m.cond_drop_prob), self.sampling_timesteps,
@@ -410,6 +486,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                float(self.guidance_rescale))
         if gated:
             key = key + ('guidance_interval',)
+        if apg:
+            key = key + (('apg',) + apg,)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -429,6 +507,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 st['gws'] = ops.guidance_workspace(st['img'])
             if gated:                                        # guidance interval: a flag per entry (all guided until fill writes it)
                 st['guided'] = torch.ones((len(times),), device=device, dtype=torch.uint8)
+            if apg:                                          # adaptive projected guidance: the guided logits, (A, Cc) per row,
+                st['apg_guided'] = torch.zeros(shape, device=device)         # the fp64 partial sums, the running average
+                st['apg_coef'] = torch.ones((shape[0], 2), device=device)
+                st['apg_ws'] = ops.apg_workspace(st['img'])
+                st['apg_run'] = torch.zeros(shape, device=device) if apg[2] != 0. else None
             gate = (st['cursor'], st['guided']) if gated else None
 
             def network():                                   # -> the logits the update reads
@@ -440,6 +523,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
             def step(cond, null, computed, noise, out):      # the update of the entry at the cursor
                 hist = st['hist'] if solver else None
+                if apg:                                      # the projected logits, then the update without a null pass
+                    ops.apg_coef_dev(st['cur'], cond, null, *apg, keep=computed, run=st['apg_run'], ws=st['apg_ws'],
+                                     coef=st['apg_coef'])
+                    cond = ops.apg_apply(cond, null, st['apg_coef'], keep=computed, run=st['apg_run'], out=st['apg_guided'])
+                    null = computed = None
                 if phi:
                     ops.guidance_factor_dev(st['cur'], cond, null, phi, keep=computed, ws=st['gws'], gfac=st['gfac'])
                     if rank is not None:
@@ -471,6 +559,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 dst.copy_(src)
             ops.affine(st['ins'][1], 2., -1., out=st['rf'])  # normalize_to_neg_one_to_one, CFG:716
             st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
+            if apg and st['apg_run'] is not None:
+                st['apg_run'].zero_()                        # the running average starts every loop at zero
             if gated:
                 flags = self._guided_entries(self._graph_tables(cond_scale, clip)[1], cond_scale)
                 st['guided'].copy_(torch.tensor(flags, dtype=torch.uint8))

@@ -729,6 +729,77 @@ def guidance_gate(cursor, guided, cond, null):
     return null
 
 
+def apg_splits(B, n):
+    """workgroups per row of the first pass of the APG coefficients (dmh_apg_splits): a pure function of (B, n)"""
+    s = int(_lib.lib().dmh_apg_splits(int(B), int(n)))
+    if s < 1:
+        raise ValueError(f'apg_splits: B = {B} rows of n = {n} elements')
+    return s
+
+
+def apg_workspace(x):
+    """the fp64 workspace dmh_apg_coef[_dev] asks for with logits of x's shape (B, ...): 3 doubles per (row, split)"""
+    B = x.shape[0]
+    return torch.empty((3 * B * apg_splits(B, x.numel() // B),), device=x.device, dtype=torch.float64)
+
+
+def _apg_shapes(who, model_cond, model_null, run):
+    if model_null is None or tuple(model_null.shape) != tuple(model_cond.shape):
+        raise ValueError(f'{who}: model_null {None if model_null is None else tuple(model_null.shape)} against model_cond '
+                         f'{tuple(model_cond.shape)} (the projection needs the null pass)')
+    if run is not None and tuple(run.shape) != tuple(model_cond.shape):
+        raise ValueError(f'{who}: run {tuple(run.shape)} against model_cond {tuple(model_cond.shape)}')
+
+
+def _apg_buffers(who, model_cond, model_null, beta, run, ws, coef):
+    _apg_shapes(who, model_cond, model_null, run)
+    if (run is not None) != (float(beta) != 0.):
+        raise ValueError(f'{who}: run is {"given" if run is not None else "None"} with beta = {beta!r} (the running average goes '
+                         f'with beta != 0, and only with it)')
+    B = model_cond.shape[0]
+    ws = apg_workspace(model_cond) if ws is None else ws
+    coef = _empty((B, 2), model_cond) if coef is None else coef
+    need = 3 * B * apg_splits(B, model_cond.numel() // B)
+    if ws.numel() < need or tuple(coef.shape) != (B, 2):
+        raise ValueError(f'{who}: ws of {ws.numel()} doubles ({need} needed) / coef {tuple(coef.shape)} for {B} rows')
+    return ws, coef
+
+
+def apg_coef(step, model_cond, model_null, eta, rho=0., beta=0., keep=None, run=None, ws=None, coef=None):
+    """the coefficients of adaptive projected guidance for one denoise step (dmh_apg_coef; the definition: include/dmhomo_hip.h):
+    coef[b] = (A, Cc) with guided = A * c + Cc * d, c the conditional logits (``keep`` as sampler_step), d = c - null, or — beta
+    != 0 — the running average ``run`` (model_cond's shape, zero in front of the first step), overwritten in place with d + beta
+    * run.  eta in [0, 1] weights the part of d parallel to c, rho >= 0 caps the update's norm per row (0: no cap); only
+    step.cond_scale is read.  fp64 sums, bitwise repeatable.  ws: apg_workspace(model_cond).  -> coef (B, 2)"""
+    ws, coef = _apg_buffers('apg_coef', model_cond, model_null, beta, run, ws, coef)
+    call('dmh_apg_coef', C.byref(step), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), float(eta), float(rho),
+         float(beta), ptr(run), ptr(ws, torch.float64), ptr(coef), model_cond.shape[0], model_cond.numel() // model_cond.shape[0])
+    return coef
+
+
+def apg_coef_dev(cur, model_cond, model_null, eta, rho=0., beta=0., keep=None, run=None, ws=None, coef=None):
+    """apg_coef with its DmhStep in device memory (``cur`` of step_table)"""
+    ws, coef = _apg_buffers('apg_coef_dev', model_cond, model_null, beta, run, ws, coef)
+    call('dmh_apg_coef_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), float(eta), float(rho),
+         float(beta), ptr(run), ptr(ws, torch.float64), ptr(coef), model_cond.shape[0], model_cond.numel() // model_cond.shape[0])
+    return coef
+
+
+def apg_apply(model_cond, model_null, coef, keep=None, run=None, out=None):
+    """the guided logits of adaptive projected guidance (dmh_apg_apply): A * c + Cc * d with coef (B, 2) of apg_coef and d = ``run``
+    where the step keeps a running average (the one apg_coef just wrote), else c - null.  It reads no DmhStep: the same call
+    serves the eager and the replayed loop.  out must not be one of the inputs.  The result goes to sampler_step / sampler_step_ms
+    / sampler_threshold + sampler_step_thr as model_cond with model_null = None.  -> guided (model_cond's shape)"""
+    _apg_shapes('apg_apply', model_cond, model_null, run)
+    B = model_cond.shape[0]
+    out = torch.empty_like(model_cond) if out is None else out
+    if tuple(coef.shape) != (B, 2) or tuple(out.shape) != tuple(model_cond.shape):
+        raise ValueError(f'apg_apply: coef {tuple(coef.shape)} / out {tuple(out.shape)} against model_cond {tuple(model_cond.shape)}')
+    call('dmh_apg_apply', ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), ptr(run), ptr(coef), ptr(out), B,
+         model_cond.numel() // B)
+    return out
+
+
 def rng_indexed(shape, sample_ids, state, kind=0):
     """one draw of the sample-indexed generator (dmh_rng_indexed): (B, *shape[1:]) fp32 whose row b is a pure function of
     (state[0] = seed, sample_ids[b], state[1] = draw index, element); the launch advances the draw index.

@@ -438,6 +438,47 @@ int dmh_rows_gated(const uint8_t* keep, int B, int extra, const int32_t* cursor,
 int dmh_guidance_gate(const int32_t* cursor, const uint8_t* guided, int S, const float* cond, float* null, int64_t n,
                       void* stream);
 
+/* Adaptive projected guidance, APG (Sadat, Hilliges, Weber 2024, "Eliminating Oversaturation and Artifacts of High Guidance
+ * Scales in Diffusion Models", Algorithm 1; not in the reference): the guidance update cond - null is split into its parts
+ * parallel and orthogonal to the conditional logits; the parallel part is down-weighted (eta), the update's norm is capped per
+ * sample (rho, 0: no cap) and a negative-momentum average of the update runs over the steps (beta, 0: none).  Per row b of n
+ * values (one sample: n = C*H*W):
+ *   c[i] = model_cond[i], or model_null[i] where keep[b] == 0        (the conditional logit as dmh_sampler_step reads it)
+ *   u[i] = model_null[i]
+ *   d[i] = c[i] - u[i]                                               fp32
+ *   beta != 0:  r[i] = d[i] + beta * r_prev[i]  (fp32, the product rounded before the sum; r_prev = 0 at the first step); d <- r
+ *   Sdd = sum d^2, Sdc = sum d*c, Scc = sum c^2                      each product and the sums in fp64
+ *   s   = 1 if rho == 0 or Sdd == 0, else min(1, rho / sqrt(Sdd))
+ *   p   = 0 if Scc == 0, else Sdc / Scc                              (the projection of d on c)
+ *   A[b]  = 1 - (w - 1) * s * (1 - eta) * p                          w = cond_scale; fp64, rounded to fp32 once
+ *   Cc[b] = (w - 1) * s                                              fp64, rounded to fp32 once
+ *   guided[i] = A[b] * c[i] + Cc[b] * d[i]                           fp32: two products and one add, no contraction
+ * which is c + (w - 1) * s * (d_orth + eta * d_par).  With eta = 1, rho = 0, beta = 0 it is the guided blend in exact arithmetic,
+ * not bit for bit.  A row whose cond equals its null bitwise has d == 0 at beta == 0: A == 1 and guided == c exactly (the dropped
+ * rows of the conditional pass).  A row whose sums are not all finite (a NaN or an infinity in it) gets A = Cc = NaN, and no
+ * other row does.  The guided logits are handed to dmh_sampler_step / _ms / _thr / dmh_sampler_threshold (and their _dev forms)
+ * as model_cond with model_null == NULL: those do the plain step on them.
+ *
+ * dmh_apg_splits(B, n): the workgroups per row of the first pass, a pure function of (B, n); -1 for B < 1 or n outside
+ * [1, 2^31).
+ * dmh_apg_coef[_dev]: coef [2 * B] <- (A[b], Cc[b]) at coef[2 * b], coef[2 * b + 1].  Only cond_scale is read from the DmhStep (by
+ * value, or from device memory as dmh_sampler_step_dev reads it).  model_null is required, 0 <= eta <= 1, rho >= 0 and finite,
+ * |beta| < 1.  run [B * n]: the running average r, read and overwritten in place; required with beta != 0 and refused with beta
+ * == 0; the caller zeroes it in front of the first step.  ws: workspace of the caller, 3 * B * dmh_apg_splits(B, n) doubles.  Two
+ * launches: per (row, split) the three fp64 sums into ws (and run, each element by the thread that read it), 16-byte loads where
+ * cond, null and run meet 16-byte boundaries together; then one thread per row adds them in split order.  No atomics, no
+ * arrival counter: bitwise repeatable, and a row's coefficients do not depend on the rows beside it.
+ * dmh_apg_apply: guided [B * n] <- A[b] * c + Cc[b] * d, d = run[i] where run != NULL (the r dmh_apg_coef just wrote), else c - u
+ * again.  It reads no DmhStep (cond_scale sits in coef), so one entry serves the eager and the replayed loop.  guided must not
+ * overlap model_cond, model_null or run. */
+int dmh_apg_splits(int B, int64_t n);
+int dmh_apg_coef(const DmhStep* s, const float* model_cond, const float* model_null, const uint8_t* keep, float eta, float rho,
+                 float beta, float* run, double* ws, float* coef, int B, int64_t n, void* stream);
+int dmh_apg_coef_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const uint8_t* keep, float eta,
+                     float rho, float beta, float* run, double* ws, float* coef, int B, int64_t n, void* stream);
+int dmh_apg_apply(const float* model_cond, const float* model_null, const uint8_t* keep, const float* run, const float* coef,
+                  float* guided, int B, int64_t n, void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -19,6 +19,10 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
   * --guidance_interval LO HI applies the guidance only at the entries whose normalised time t / (T - 1) lies in [LO, HI]; the
     others run the conditional pass alone, at half the UNet rows (limited-interval guidance, Kynkaanniemi et al. 2024; an
     addition); the default, off, guides every entry as the reference does;
+  * --apg_eta ETA in [0, 1] replaces the guided blend by adaptive projected guidance (Sadat et al. 2024; an addition): the part of
+    cond - null parallel to the conditional output is weighted by ETA, --apg_norm_threshold RHO > 0 caps the update's norm per
+    sample and --apg_momentum BETA in (-1, 1) averages it over the steps; the default, off, is the reference's blend.  Not
+    together with --guidance_rescale or --guidance_interval;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -74,6 +78,13 @@ parser.add_argument('--guidance_rescale', type=float, default=0.,
 parser.add_argument('--guidance_interval', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                     help='guide only where LO <= t / (T - 1) <= HI, 0 <= LO <= HI <= 1 (Kynkaanniemi et al. 2024; not in the '
                          'reference; ScheduleHost.guidance_interval); default: every entry')
+parser.add_argument('--apg_eta', type=float, default=None,
+                    help='weight in [0, 1] of the part of the guidance update parallel to the conditional output: adaptive projected '
+                         'guidance (Sadat et al. 2024 use 0; not in the reference; GaussianDiffusion.apg_eta); default: off')
+parser.add_argument('--apg_norm_threshold', type=float, default=0.,
+                    help='with --apg_eta: cap of the norm of the guidance update per sample, >= 0; 0: no cap')
+parser.add_argument('--apg_momentum', type=float, default=0.,
+                    help='with --apg_eta: momentum in (-1, 1) of the running average of the update (the paper uses -0.5); 0: none')
 args = parser.parse_args()
 
 num_classes = 1
@@ -105,6 +116,7 @@ def main():
     sampler.clip_mode, sampler.dynamic_threshold_percentile = args.clip_mode, args.dynamic_threshold_percentile
     sampler.guidance_rescale = args.guidance_rescale
     sampler.guidance_interval = None if args.guidance_interval is None else tuple(args.guidance_interval)
+    sampler.apg_eta, sampler.apg_norm_threshold, sampler.apg_momentum = args.apg_eta, args.apg_norm_threshold, args.apg_momentum
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
