@@ -181,6 +181,14 @@ SIGNATURES = {
     'dmh_apg_coef_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, c_float, c_float, c_float, c_f32p, C.c_void_p, c_f32p,
                                  c_int, c_i64, C.c_void_p]),
     'dmh_apg_apply': (c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_int, c_i64, C.c_void_p]),
+    'dmh_photo_acc_words': (c_i64, [c_int, c_int, c_int]),
+    'dmh_photo_energy_splits': (c_int, [c_int, c_int, c_int]),
+    'dmh_photo_weights': (c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_photo_guide': (c_int, [C.POINTER(DmhStep), c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_float, C.c_void_p,
+                                c_f32p, c_int, c_int, c_int, C.c_void_p]),
+    'dmh_photo_guide_dev': (c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_float, C.c_void_p, c_f32p,
+                                    c_int, c_int, c_int, C.c_void_p]),
+    'dmh_photo_energy': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, C.c_void_p]),
     'dmh_rng_indexed': (c_int, [c_f32p, c_int, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     'dmh_rng_keep_mask': (c_int, [C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_float, C.c_void_p]),
     'dmh_rows_lincomb': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, C.c_void_p]),

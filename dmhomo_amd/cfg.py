@@ -271,6 +271,67 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         coef = ops.apg_coef(step, cond, null, eta, rho, beta, keep=computed, run=ast['run'], ws=ast['ws'])
         return ops.apg_apply(cond, null, coef, keep=computed, run=ast['run'], out=ast['guided']), coef
 
+    # OPT-IN, None by default (every existing result, launch and graph key stays what it is).  photo_guidance = w in (0, 1]:
+    # photometric-consistency guidance in sample() — training adds alpha_bar_t * mean(mask * l(flow_warp(im2, flow) - im1)) to the
+    # loss (CFG:782-806), the reference's sampler ignores flow and mask beyond the stem.  With the switch on, at every entry of the
+    # time list the blended x_start prediction is moved down the gradient of that term's squared form, E = mean(mask *
+    # (flow_warp(im2, flow) - im1) ** 2): im1 towards the warped im2, im2 the transposed way, by lambda / 2 of the masked residual
+    # with lambda = w * alpha_bar_t, the weight the loss gives the term; the im2 side is divided by max(1, s), s the mask-weighted
+    # bilinear weight that lands on a pixel, which makes the step a descent of E for every flow (include/dmhomo_hip.h has the
+    # definition and the argument).  The corrected logits (dmh_photo_guide) go through the existing step and threshold kernels as
+    # a conditional output without a null pass, so both samplers, both clip modes, dedup_dropped_rows and both cfg_modes take it;
+    # it needs no null pass and acts at cond_scale == 1 too.  Refused with another objective than pred_x0 (the logits are then
+    # not the image pair), with guidance_rescale > 0 and apg_eta (they rescale / project the blend this step corrects: which goes
+    # first has no definition yet) and with guidance_interval (the captured step would need the gate's null copy in front of the
+    # correction).  model_predictions and forward_with_cond_scale do not know it.  ddpm.photometric_error gives E of any pair.
+    # What it does to samples of trained weights has not been measured.
+    photo_guidance = None
+
+    def _check_photo_guidance(self):
+        """-> None (off), or the weight w as a float"""
+        w = self.photo_guidance
+        if w is None:
+            return None
+        if not (isinstance(w, (int, float)) and not isinstance(w, bool) and 0. < w <= 1.):
+            raise ValueError(f'photo_guidance = {w!r}: None (off), or a number in (0, 1]')
+        if self.objective != 'pred_x0':
+            raise ValueError(f'photo_guidance = {w!r} with objective = {self.objective!r}: the correction acts on the predicted '
+                             f'image pair, which the network returns under pred_x0 only')
+        if self._check_guidance_rescale() > 0.:
+            raise ValueError(f'photo_guidance = {w!r} together with guidance_rescale = {self.guidance_rescale!r}: the rescale '
+                             f'works on the blend that the correction replaces, the order of the two is not defined')
+        if self.apg_eta is not None:
+            raise ValueError(f'photo_guidance = {w!r} together with apg_eta = {self.apg_eta!r}: both hand guided logits to the '
+                             f'step in place of the blend, the order of the two is not defined')
+        if self._check_guidance_interval() is not None:
+            raise ValueError(f'photo_guidance = {w!r} together with guidance_interval = {self.guidance_interval!r}: the '
+                             f'correction is defined on the blend of every entry, not across unguided entries')
+        return float(w)
+
+    @staticmethod
+    def _photo_state(shape, flow, mask, device):
+        """the buffers one eager loop keeps: flow and mask as fp32, the preconditioner s (computed here, once per call), the
+        zeroed fixed-point accumulator and the guided logits"""
+        flow = flow.to(torch.float32).contiguous()
+        mask = mask.to(torch.float32).contiguous()
+        acc = ops.photo_acc(shape[0], shape[2], shape[3], device)
+        return {'flow': flow, 'mask': mask, 'acc': acc, 's': ops.photo_weights(flow, mask, acc),
+                'guided': torch.empty(shape, device=device, dtype=torch.float32)}
+
+    def _photo_logits(self, step, cond, null, computed, w, pst, cond_scale, want_energy):
+        """one eager step's corrected logits -> (guided, what the trace adds); the update behind it takes (guided, None,
+        keep=None).  want_energy: E of the blend before the correction (two launches more, and the blend itself where there is
+        a null pass: tracing only)"""
+        more = {}
+        if want_energy:
+            blend = cond
+            if null is not None:
+                blend, _, _ = ops.sampler_step(self._blend_step(cond_scale), cond, null, null, None, want_x_start=False,
+                                               keep=computed)
+            more['photo'] = ops.photo_energy(blend, pst['flow'], pst['mask'])
+        return ops.photo_guide(step, cond, null, computed, pst['flow'], pst['mask'], pst['s'], w, pst['acc'],
+                               out=pst['guided']), more
+
     def _network(self, x, t, classes, rgb_flow, mask, cond_scale, gate=None):
         """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null (``gate`` too)"""
         if cond_scale == 1:
@@ -326,16 +387,19 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
     def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
         'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac' at the guided entries; 'guided': whether
-        the entry ran with the null pass, False only under guidance_interval; with apg_eta, the step's (A, Cc) per row, 'apg' (B, 2))."""
+        the entry ran with the null pass, False only under guidance_interval; with apg_eta, the step's (A, Cc) per row, 'apg' (B, 2);
+        with photo_guidance, the photometric energy of the blend before the correction, 'photo' (B,) float64)."""
         batch, device = shape[0], self.betas.device
         steps = self._ddim_steps(clip_denoised, cond_scale)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
         apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
+        photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
         img = self.rng.randn(shape, device).contiguous()
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
+        pst = self._photo_state(shape, flow, mask, device) if photo else None
         for k, (time, step, draws) in enumerate(steps):
             on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
@@ -345,6 +409,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if apg:                                          # the projected logits, then the update without a null pass
                 cond, coef = self._apg_logits(step, cond, null, computed, apg, ast)
                 null, computed, more = None, None, {'apg': coef}
+            if photo:                                        # the corrected logits, then the update without a null pass
+                cond, more = self._photo_logits(step, cond, null, computed, photo, pst, cond_scale, trace is not None)
+                null, computed = None, None
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
                                                             trace is not None)
@@ -398,10 +465,12 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
         apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
+        photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
+        pst = self._photo_state(shape, flow, mask, device) if photo else None
         for k, (time, step, _) in enumerate(steps):
             on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
@@ -410,6 +479,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if apg:                                          # the projected logits, then the update without a null pass
                 cond, coef = self._apg_logits(step, cond, null, computed, apg, ast)
                 null, computed, more = None, None, {'apg': coef}
+            if photo:                                        # the corrected logits, then the update without a null pass
+                cond, more = self._photo_logits(step, cond, null, computed, photo, pst, cond_scale, trace is not None)
+                null, computed = None, None
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
                                                             trace is not None)
@@ -470,7 +542,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         lists of the network: no null rows at an unguided entry) and by dmh_guidance_gate behind the network (null <- cond there),
         and every launch behind the gate is the one it was.  With apg_eta (and a null pass) the update starts with dmh_apg_coef_dev and
         dmh_apg_apply on static buffers (the guided logits, the coefficients, the fp64 workspace and, with momentum, the running
-        average, which fill zeroes on every call), and the launches behind them are those of cond_scale == 1 on the guided logits."""
+        average, which fill zeroes on every call), and the launches behind them are those of cond_scale == 1 on the guided logits.
+        With photo_guidance the update starts with dmh_photo_guide_dev on static buffers (flow and mask as fp32, the preconditioner
+        s, the fixed-point accumulator, the guided logits): fill copies flow and mask and recomputes s on every call, the weight
+        is a launch argument and so part of the key."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
@@ -488,6 +563,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             key = key + ('guidance_interval',)
         if apg:
             key = key + (('apg',) + apg,)
+        photo = self._check_photo_guidance()                 # None: off.  (It refuses phi, apg_eta and an interval beside it.)
+        if photo:
+            key = key + (('photo', photo),)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -512,6 +590,12 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 st['apg_coef'] = torch.ones((shape[0], 2), device=device)
                 st['apg_ws'] = ops.apg_workspace(st['img'])
                 st['apg_run'] = torch.zeros(shape, device=device) if apg[2] != 0. else None
+            if photo:                                        # photometric guidance: flow and mask as fp32, s, the accumulator
+                st['photo_flow'] = flow.to(torch.float32).clone()            # (zero between launches), the guided logits
+                st['photo_mask'] = mask.to(torch.float32).clone()
+                st['photo_acc'] = ops.photo_acc(shape[0], shape[2], shape[3], device)
+                st['photo_s'] = ops.photo_weights(st['photo_flow'], st['photo_mask'], st['photo_acc'])
+                st['photo_guided'] = torch.zeros(shape, device=device)
             gate = (st['cursor'], st['guided']) if gated else None
 
             def network():                                   # -> the logits the update reads
@@ -527,6 +611,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                     ops.apg_coef_dev(st['cur'], cond, null, *apg, keep=computed, run=st['apg_run'], ws=st['apg_ws'],
                                      coef=st['apg_coef'])
                     cond = ops.apg_apply(cond, null, st['apg_coef'], keep=computed, run=st['apg_run'], out=st['apg_guided'])
+                    null = computed = None
+                if photo:                                    # the corrected logits, then the update without a null pass
+                    cond = ops.photo_guide_dev(st['cur'], cond, null, computed, st['photo_flow'], st['photo_mask'], st['photo_s'],
+                                               photo, st['photo_acc'], out=st['photo_guided'])
                     null = computed = None
                 if phi:
                     ops.guidance_factor_dev(st['cur'], cond, null, phi, keep=computed, ws=st['gws'], gfac=st['gfac'])
@@ -561,6 +649,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
             if apg and st['apg_run'] is not None:
                 st['apg_run'].zero_()                        # the running average starts every loop at zero
+            if photo:                                        # this call's flow and mask, and the preconditioner they give
+                st['photo_flow'].copy_(flow)
+                st['photo_mask'].copy_(mask)
+                ops.photo_weights(st['photo_flow'], st['photo_mask'], st['photo_acc'], out=st['photo_s'])
             if gated:
                 flags = self._guided_entries(self._graph_tables(cond_scale, clip)[1], cond_scale)
                 st['guided'].copy_(torch.tensor(flags, dtype=torch.uint8))

@@ -416,6 +416,15 @@ def flow_warp(x, flow12, pad='border', mode='bilinear'):
     return ops.flow_warp(x.to(torch.float32).contiguous(), flow12.to(torch.float32).contiguous(), pad=pad, mode=mode)
 
 
+def photometric_error(images, flow, mask):
+    """How far an image pair is from obeying its flow label: E[b] = mean over (3, H, W) of mask * (flow_warp(images[:, 3:], flow)
+    - images[:, :3]) ** 2, the squared form of the photometric term of the training loss (CFG:782-806), per sample and in
+    float64 (dmh_photo_energy; not in the reference).  images (B, 6, H, W) — what cfg.GaussianDiffusion.sample returns, for
+    example, on whatever scale it has —, flow (B, 2, H, W), mask (B, 1, H, W).  -> (B,) float64"""
+    f32 = lambda t: t.to(torch.float32).contiguous()
+    return ops.photo_energy(f32(images), f32(flow), f32(mask))
+
+
 def homo_gen(flow):
     """G5, DDP:1647-1661: flow (B,2,H,W) -> (B,1,3,3) float64."""
     return ops.dlt_homography(flow.to(torch.float32).contiguous()).reshape(-1, 1, 3, 3)
@@ -597,9 +606,14 @@ class Trainer(object):
     reference's dataset directory (the CA-Homo dataset path is outside the hot path); ``train`` is a §8f row.
 
     ``preview`` (class attribute, off by default): write the reference's sample sheets — ``train`` at every
-    ``save_and_sample_every``-th step (DDP:1871-1935), ``sample`` at every 100th ``step`` (DDP:1972-2019)."""
+    ``save_and_sample_every``-th step (DDP:1871-1935), ``sample`` at every 100th ``step`` (DDP:1972-2019).
+
+    ``score_photometric`` (class attribute, off by default): ``sample`` also leaves ``photometric_error`` of the batch it drew,
+    (B,) float64, in ``last_photometric_error``; the record returned is the same either way."""
 
     preview = False
+    score_photometric = False
+    last_photometric_error = None
 
     def __init__(self, diffusion_model, folder, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_horizontal_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10,
@@ -758,6 +772,8 @@ class Trainer(object):
         with torch.no_grad():
             all_images = self.ema.ema_model.sample(classes=data[1].to(dev), rgb_flow=rgb_flows, flow=flows, mask=mask)
         ret = saveTrainPair(all_images[0], mask=all_images[1], flows=all_images[2])
+        if self.score_photometric:
+            self.last_photometric_error = photometric_error(all_images[0], all_images[2], all_images[1])
         if dump:
             n = square_rows(all_images[0].shape[0])
             nrow = int(math.sqrt(n))

@@ -800,6 +800,99 @@ def apg_apply(model_cond, model_null, coef, keep=None, run=None, out=None):
     return out
 
 
+def _photo_dims(who, x, flow, mask):
+    """(B, H, W) of logits (B, 6, H, W) with flow (B, 2, H, W) and mask (B, 1, H, W)"""
+    if x.dim() != 4 or x.shape[1] != 6:
+        raise ValueError(f'{who}: {tuple(x.shape)} (the image pair is (B, 6, H, W))')
+    B, _, H, W = x.shape
+    if tuple(flow.shape) != (B, 2, H, W) or tuple(mask.shape) != (B, 1, H, W):
+        raise ValueError(f'{who}: flow {tuple(flow.shape)} / mask {tuple(mask.shape)} against {tuple(x.shape)}')
+    return B, H, W
+
+
+def photo_acc(B, H, W, device):
+    """the zeroed Q31.32 accumulator of photo_weights / photo_guide for B samples of H x W pixels (dmh_photo_acc_words 64-bit
+    words); every call that uses it leaves it zero"""
+    n = int(_lib.lib().dmh_photo_acc_words(int(B), int(H), int(W)))
+    if n < 1:
+        raise ValueError(f'photo_acc: B = {B} samples of {H} x {W} pixels')
+    return torch.zeros((n,), device=device, dtype=torch.int64)
+
+
+def photo_weights(flow, mask, acc=None, out=None):
+    """s[b, q] = sum_p mask[b, p] * w_p(q) (dmh_photo_weights): how much mask-weighted bilinear weight of flow_warp(., flow) lands
+    on pixel q — the preconditioner of photo_guide, a function of flow (B, 2, H, W) and mask (B, 1, H, W) alone.  Integer
+    fixed-point sums: bitwise repeatable.  -> s (B, H, W)"""
+    if flow.dim() != 4 or flow.shape[1] != 2 or tuple(mask.shape) != (flow.shape[0], 1) + tuple(flow.shape[2:]):
+        raise ValueError(f'photo_weights: flow {tuple(flow.shape)} / mask {tuple(mask.shape)}')
+    B, _, H, W = flow.shape
+    acc = photo_acc(B, H, W, flow.device) if acc is None else acc
+    out = _empty((B, H, W), flow) if out is None else out
+    if tuple(out.shape) != (B, H, W) or acc.numel() < B * H * W:
+        raise ValueError(f'photo_weights: out {tuple(out.shape)} / acc of {acc.numel()} words for {B} x {H} x {W}')
+    call('dmh_photo_weights', ptr(flow), ptr(mask), ptr(acc, torch.int64), ptr(out), B, H, W)
+    return out
+
+
+def _photo_guide_buffers(who, model_cond, model_null, flow, mask, s, acc, out):
+    B, H, W = _photo_dims(who, model_cond, flow, mask)
+    if model_null is not None and tuple(model_null.shape) != tuple(model_cond.shape):
+        raise ValueError(f'{who}: model_null {tuple(model_null.shape)} against model_cond {tuple(model_cond.shape)}')
+    out = torch.empty_like(model_cond) if out is None else out
+    if tuple(s.shape) != (B, H, W) or tuple(out.shape) != tuple(model_cond.shape) or acc.numel() < 3 * B * H * W:
+        raise ValueError(f'{who}: s {tuple(s.shape)} / out {tuple(out.shape)} / acc of {acc.numel()} words against model_cond '
+                         f'{tuple(model_cond.shape)}')
+    return B, H, W, out
+
+
+def photo_guide(step, model_cond, model_null, keep, flow, mask, s, w, acc, out=None):
+    """the logits of one denoise step after photometric-consistency guidance (dmh_photo_guide; the definition:
+    include/dmhomo_hip.h): the guided blend of (model_cond, model_null, keep) as sampler_step reads it — model_null and keep may
+    be None — with im1 = x[:, :3] moved towards flow_warp(im2, flow) and im2 = x[:, 3:] moved the transposed way, by lambda / 2
+    = w * step.sqrt_ac ** 2 / 2 of the masked residual, the im2 side divided by max(1, s) (``s`` of photo_weights).  acc:
+    photo_acc(...), zero before and after.  Only step.cond_scale and step.sqrt_ac are read.  Bitwise repeatable.  The result
+    goes to sampler_step / sampler_step_ms / sampler_threshold + sampler_step_thr as model_cond with model_null = None.
+    -> guided (model_cond's shape)"""
+    B, H, W, out = _photo_guide_buffers('photo_guide', model_cond, model_null, flow, mask, s, acc, out)
+    call('dmh_photo_guide', C.byref(step), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), ptr(flow), ptr(mask), ptr(s),
+         float(w), ptr(acc, torch.int64), ptr(out), B, H, W)
+    return out
+
+
+def photo_guide_dev(cur, model_cond, model_null, keep, flow, mask, s, w, acc, out=None):
+    """photo_guide with its DmhStep in device memory (``cur`` of step_table)"""
+    B, H, W, out = _photo_guide_buffers('photo_guide_dev', model_cond, model_null, flow, mask, s, acc, out)
+    call('dmh_photo_guide_dev', ptr(cur, torch.uint8), ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), ptr(flow),
+         ptr(mask), ptr(s), float(w), ptr(acc, torch.int64), ptr(out), B, H, W)
+    return out
+
+
+def photo_energy_splits(B, H, W):
+    """workgroups per sample of the energy's first pass (dmh_photo_energy_splits): a pure function of (B, H, W)"""
+    n = int(_lib.lib().dmh_photo_energy_splits(int(B), int(H), int(W)))
+    if n < 1:
+        raise ValueError(f'photo_energy_splits: B = {B} samples of {H} x {W} pixels')
+    return n
+
+
+def photo_energy_workspace(x):
+    """the fp64 workspace dmh_photo_energy asks for with an image pair of x's shape (B, 6, H, W): one double per (sample, split)"""
+    B, _, H, W = x.shape
+    return torch.empty((B * photo_energy_splits(B, H, W),), device=x.device, dtype=torch.float64)
+
+
+def photo_energy(x, flow, mask, ws=None, out=None):
+    """the photometric energy per sample (dmh_photo_energy): E[b] = mean over (3, H, W) of mask * (flow_warp(x[:, 3:], flow) -
+    x[:, :3]) ** 2, warp and sums in float64, a fixed summation order.  -> E (B,) float64"""
+    B, H, W = _photo_dims('photo_energy', x, flow, mask)
+    ws = photo_energy_workspace(x) if ws is None else ws
+    out = _empty((B,), x, torch.float64) if out is None else out
+    if tuple(out.shape) != (B,) or ws.numel() < B * photo_energy_splits(B, H, W):
+        raise ValueError(f'photo_energy: out {tuple(out.shape)} / ws of {ws.numel()} doubles for {B} x {H} x {W}')
+    call('dmh_photo_energy', ptr(x), ptr(flow), ptr(mask), ptr(ws, torch.float64), ptr(out, torch.float64), B, H, W)
+    return out
+
+
 def rng_indexed(shape, sample_ids, state, kind=0):
     """one draw of the sample-indexed generator (dmh_rng_indexed): (B, *shape[1:]) fp32 whose row b is a pure function of
     (state[0] = seed, sample_ids[b], state[1] = draw index, element); the launch advances the draw index.

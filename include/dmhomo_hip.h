@@ -479,6 +479,52 @@ int dmh_apg_coef_dev(const DmhStep* cur_dev, const float* model_cond, const floa
 int dmh_apg_apply(const float* model_cond, const float* model_null, const uint8_t* keep, const float* run, const float* coef,
                   float* guided, int B, int64_t n, void* stream);
 
+/* Photometric-consistency guidance (not in the reference's sampler): at every denoise step the predicted x_start is moved down
+ * the gradient of the photometric energy of the training loss (CFG:782-806, squared form), with the weight the loss gives that
+ * term.  Per sample, x [6][H][W] the blended logits (objective pred_x0: the x_start prediction; x[:3] is im1, x[3:] im2):
+ *   c = model_cond, or model_null where keep[b] == 0;  x = c where model_null == NULL, else null + (c - null) * cond_scale
+ *                                                       (the device function of the step kernels, csrc/sampler_dev.h)
+ *   w_p(q): the bilinear weights of dmh_flow_warp(pad border, mode bilinear) for the pixel p moved by flow(p): the sample point
+ *           clamped to the image, its four taps, a tap one past the last row / column dropped
+ *   u[c,p]   = sum_q w_p(q) * x[3+c,q]                       fp32, the fma chain of dmh_flow_warp (im2 warped to im1's frame)
+ *   r[c,p]   = mask[p] * (u[c,p] - x[c,p])                   fp32
+ *   s[q]     = sum_p mask[p] * w_p(q)                        (flow and mask only: dmh_photo_weights, once per sampling call)
+ *   lambda   = w * (sqrt_ac * sqrt_ac)                       fp32, from the DmhStep: w * alphas_cumprod[t], the loss's weight
+ *   y[c,p]   = x[c,p]   + (lambda / 2) * r[c,p]
+ *   y[3+c,q] = x[3+c,q] - (lambda / 2) * ((sum_p w_p(q) * r[c,p]) / max(1, s[q]))
+ *   E        = (1 / (3 H W)) * sum_{c,p} mask[p] * (u[c,p] - x[c,p])^2      float64 (u too), per sample
+ * Where r (resp. the sum) is 0 the logit is handed on bit for bit.  With D = diag(1 / max(1, s)) and A = M^1/2 W D^1/2, the rows
+ * of W summing to at most 1 give |A v|^2 <= sum_q d_q s_q v_q^2 <= |v|^2: the preconditioned Hessian has norm <= 2 and the step
+ * lowers E for every flow and every lambda in (0, 1] (without the division it diverges where many pixels sample one target).
+ *
+ * Summation.  The two scatters (s, and sum_p w_p(q) * r) add with 64-bit INTEGER atomics in Q31.32 fixed point, so a launch's
+ * result does not depend on the order in which workgroups run and is bitwise repeatable.  A contribution v (an fp32 product) is
+ * rint(clamp(v, -2^30, 2^30) * 2^32); a NaN contributes 0 (it still shows in y[c,p] of its own pixel).  Exact to 2^-33 per
+ * contribution while sum |v| < 2^31 at a target; beyond that the sum wraps (defined, and wrong).
+ *
+ * dmh_photo_acc_words(B, H, W): the 64-bit words of the accumulator, 3 * B * H * W; -1 for sizes the entries refuse.  acc is the
+ * caller's, ZERO in front of the first call; every entry that uses it leaves it zero (the pass that finishes im2, resp. s, zeroes
+ * what it read), so a sampling loop needs no memset.
+ * dmh_photo_weights: s [B][H][W] from flow [B][2][H][W] and mask [B][1][H][W].  Two launches.
+ * dmh_photo_guide[_dev]: guided [B][6][H][W] <- y.  cond_scale and sqrt_ac are read from the DmhStep (by value, or from device
+ * memory as dmh_sampler_step_dev reads it) and nothing else.  model_null and keep may be NULL (keep needs model_null); 0 < w <= 1;
+ * guided must not overlap model_cond or model_null.  Two launches: one thread per pixel p (blend, warp, residual, y[:3], scatter),
+ * then one per element of im2.  The guided logits go to dmh_sampler_step / _ms / _thr / dmh_sampler_threshold as model_cond with
+ * model_null == NULL.
+ * dmh_photo_energy: E [B] (float64) of any x [B][6][H][W].  ws: dmh_photo_energy_splits(B, H, W) * B doubles.  Two launches: fp64
+ * partial sums per (sample, split) in a fixed order, then one thread per sample adds them in split order.  No atomics.
+ * Every entry: B in [1, 65535], H >= 2 and W >= 2 (the warp divides by W - 1), H * W <= 2^24. */
+int64_t dmh_photo_acc_words(int B, int H, int W);
+int dmh_photo_energy_splits(int B, int H, int W);
+int dmh_photo_weights(const float* flow, const float* mask, uint64_t* acc, float* s, int B, int H, int W, void* stream);
+int dmh_photo_guide(const DmhStep* s, const float* model_cond, const float* model_null, const uint8_t* keep, const float* flow,
+                    const float* mask, const float* sw, float w, uint64_t* acc, float* guided, int B, int H, int W, void* stream);
+int dmh_photo_guide_dev(const DmhStep* cur_dev, const float* model_cond, const float* model_null, const uint8_t* keep,
+                        const float* flow, const float* mask, const float* sw, float w, uint64_t* acc, float* guided, int B, int H,
+                        int W, void* stream);
+int dmh_photo_energy(const float* x, const float* flow, const float* mask, double* ws, double* E, int B, int H, int W,
+                     void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -23,6 +23,10 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     cond - null parallel to the conditional output is weighted by ETA, --apg_norm_threshold RHO > 0 caps the update's norm per
     sample and --apg_momentum BETA in (-1, 1) averages it over the steps; the default, off, is the reference's blend.  Not
     together with --guidance_rescale or --guidance_interval;
+  * --photo_guidance W in (0, 1] moves every step's predicted pair down the gradient of the photometric term of the training
+    loss, mask * (flow_warp(im2, flow) - im1) ** 2, by W * alpha_bar_t (photometric-consistency guidance; an addition), and
+    prints each batch's mean dmhomo_amd.ddpm.photometric_error; the default, off, is the reference's sampler, which ignores the
+    flow.  Not together with --guidance_rescale, --guidance_interval or --apg_eta;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -85,6 +89,10 @@ parser.add_argument('--apg_norm_threshold', type=float, default=0.,
                     help='with --apg_eta: cap of the norm of the guidance update per sample, >= 0; 0: no cap')
 parser.add_argument('--apg_momentum', type=float, default=0.,
                     help='with --apg_eta: momentum in (-1, 1) of the running average of the update (the paper uses -0.5); 0: none')
+parser.add_argument('--photo_guidance', type=float, default=None,
+                    help='weight in (0, 1] of photometric-consistency guidance: every step moves its predicted pair towards '
+                         'flow_warp(im2, flow) == im1 under the mask (not in the reference; GaussianDiffusion.photo_guidance); '
+                         'default: off')
 args = parser.parse_args()
 
 num_classes = 1
@@ -117,6 +125,8 @@ def main():
     sampler.guidance_rescale = args.guidance_rescale
     sampler.guidance_interval = None if args.guidance_interval is None else tuple(args.guidance_interval)
     sampler.apg_eta, sampler.apg_norm_threshold, sampler.apg_momentum = args.apg_eta, args.apg_norm_threshold, args.apg_momentum
+    sampler.photo_guidance = args.photo_guidance
+    trainer.score_photometric = args.photo_guidance is not None
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
@@ -131,6 +141,8 @@ def main():
         ret = trainer.sample(args.i, device, step=len(train_list))
         train_list.append(ret)
         print(f'length of trainList {len(train_list)}')
+        if trainer.score_photometric:
+            print(f'rank {rank}: mean photometric error of batch {b}: {float(trainer.last_photometric_error.mean()):.6e}')
         if len(train_list) % 2 == 0:
             np.save(f'{out_dir}idx_{args.i}_rank_{rank}_part_{part}_dm_cahomo_{len(train_list) * args.bs / 1000}k.npy',
                     np.array(train_list, dtype=object), allow_pickle=True)
