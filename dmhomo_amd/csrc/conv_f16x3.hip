@@ -25,7 +25,8 @@
 //   output       y = acc / s * 2^-k + bias
 // 22 significant bits per operand for everything within 2^18 of its block maximum, fp32 exponent range, no overflow
 // by construction.  Against an fp64 convolution the error is that of the fp32-MFMA kernels (fp32 accumulation
-// rounding dominates both): tests/test_gpu_kernels.py.
+// rounding dominates both): tests/test_gpu_kernels.py, and per output channel, per stat tile and per instance of this
+// kernel tests/test_gpu_conv_fwd.py.
 //
 //   M = output pixels: each wave owns 64 (four 16-row blocks = four tile rows);  N = 64 output channels per wave;
 //       v_mfma_f32_16x16x32_f16 (K = the 32 channels of a chunk): at equal cycles per FLOP this shape draws less
