@@ -77,14 +77,16 @@ class Unet(nn.Module):
                                  mask.to(torch.float32).contiguous(), reps=1, cpad=eng.cin_pad)
         return eng.stem(xin)
 
-    def _run(self, x, time, classes, rgb_flow, mask, keeps, taps=None, x0=None, first=None, out=None, rows=None):
+    def _run(self, x, time, classes, rgb_flow, mask, keeps, taps=None, x0=None, first=None, out=None, rows=None,
+             x0_per_pass=False):
         """rows [rep*B + b]: sample b under class-keep mask keeps[rep] -> (len(keeps)*B, out_dim, H, W).
         first: engine.first_conv(x0) when the caller shares it between passes.
-        rows: ``ops.rows_from_keep`` list of the rows to compute (the others stay unwritten), or None for all."""
+        rows: ``ops.rows_from_keep`` list of the rows to compute (the others stay unwritten), or None for all.
+        x0_per_pass: x0 holds the stem output of every pass already, len(keeps) * B rows (_cond_null_noflow)."""
         eng = self._engine
         if x0 is None:
             x0 = self._stem(x, rgb_flow, mask)
-        if len(keeps) > 1:
+        if len(keeps) > 1 and not x0_per_pass:
             x0 = x0.repeat(len(keeps), 1, 1, 1)              # row copies of the shared stem output
         time = time.to(torch.int64).contiguous()
         classes = classes.to(torch.int64).contiguous()
@@ -162,6 +164,30 @@ class Unet(nn.Module):
             rows = ops.rows_from_keep(keep, extra=B) if dedup else None
         both = self._run(x, time, classes, rgb_flow, mask, [keep, null], rows=rows)
         return both[:B], both[B:], (keep if dedup else None)
+
+    def _cond_null_noflow(self, x, time, classes, rgb_flow, mask, cond_scale):
+        """the passes of GaussianDiffusion.flow_guidance (include/dmhomo_hip.h has the definition): (cond logits, null logits or
+        None, no-flow logits, computed) as ONE launch sequence.  cond_scale != 1: 3B rows [c; n; u] — the two passes of
+        _cond_null and the null class on a stem input whose three condition channels are +0.0 — with computed as _cond_null
+        returns it.  cond_scale == 1: 2B rows [c; u] — forward's single pass and the SAME keep bits without the flow — with null
+        and computed None.  The keep mask is drawn once, where _cond_null / forward draw it; every row is bitwise the row of a
+        separate pass (rows are independent of their batch)."""
+        if self.cfg_mode == 'streams':
+            raise ValueError("flow_guidance with cfg_mode = 'streams': the third pass is defined for cfg_mode = 'batched' only")
+        B, eng = x.shape[0], self._engine
+        keep = self._keep_mask(B, self.cond_drop_prob, x.device)
+        x0 = self._stem(x, rgb_flow, mask)
+        # the no-flow stem input: assemble_input pads with zeros, so without a condition the three channels are +0.0
+        x0u = eng.stem(ops.assemble_input(x.to(torch.float32).contiguous(), None, None, cpad=eng.cin_pad))
+        if cond_scale == 1:
+            both = self._run(None, time, classes, None, None, [keep, keep], x0=torch.cat((x0, x0u)), x0_per_pass=True)
+            return both[:B], None, both[B:], None
+        null = self._null_mask(B, x.device)
+        dedup = bool(self.dedup_dropped_rows) and keep is not None
+        rows = ops.rows_from_keep(keep, extra=2 * B) if dedup else None
+        three = self._run(None, time, classes, None, None, [keep, null, null], x0=torch.cat((x0, x0, x0u)), rows=rows,
+                          x0_per_pass=True)
+        return three[:B], three[B:2 * B], three[2 * B:], (keep if dedup else None)
 
     # OPT-IN, off by default (bench.py's headline keeps it off and reports it under "variants").  The reference's conditional
     # pass draws a class-dropout mask with p = 0.5 (CFG:404 -> CFG:415,422), also while sampling: a dropped row of that pass
@@ -332,6 +358,59 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         return ops.photo_guide(step, cond, null, computed, pst['flow'], pst['mask'], pst['s'], w, pst['acc'],
                                out=pst['guided']), more
 
+    # OPT-IN, None by default (every existing result, launch, RNG draw and graph key stays what it is).  flow_guidance = s_f, a
+    # finite number >= 0: classifier-free guidance on the homography condition in sample() — the label of this data set sits in
+    # rgb_flow * mask (the class is always 0, DDP:1136), which reaches the network through three stem channels only.  With the switch
+    # on the network also runs a "no-flow" pass u (those channels +0.0, null class — at cond_scale == 1: the drawn keep bits) in the
+    # same launch sequence (Unet._cond_null_noflow: 3B rows instead of 2B, resp. 2B instead of B), and dmh_flow_guidance_shift
+    # moves the logits by e = (s_f - 1) * (n - u) (resp. (s_f - 1) * (c - u)) in front of everything else: the blend behind it is
+    # u + s_f * (n - u) + cond_scale * (c - n), the two-scale form of InstructPix2Pix (include/dmhomo_hip.h has the definition).
+    # guidance_rescale, apg_eta, photo_guidance, both clip modes, both samplers, every objective, dedup_dropped_rows and the
+    # captured step work on the shifted logits unchanged; no random draw is added (flow_guidance = 1. gives the samples of None).
+    # Refused with guidance_interval (the gated row lists have no definition for a third pass) and with cfg_mode = 'streams'.
+    # model_predictions and forward_with_cond_scale do not know it.  A model learns the no-flow pass only when it is trained with
+    # flow_drop_prob > 0 (below): on a model trained without it that pass is out of distribution.  No checkpoint trained with
+    # flow_drop_prob exists, and what the switch does to samples of trained weights has not been measured.
+    flow_guidance = None
+
+    def _check_flow_guidance(self):
+        """-> None (off), or w = flow_guidance - 1 as a float"""
+        s = self.flow_guidance
+        if s is None:
+            return None
+        if not (isinstance(s, (int, float)) and not isinstance(s, bool) and 0. <= s < float('inf')):
+            raise ValueError(f'flow_guidance = {s!r}: None (off), or a finite number >= 0')
+        if self._check_guidance_interval() is not None:
+            raise ValueError(f'flow_guidance = {s!r} together with guidance_interval = {self.guidance_interval!r}: the gated row '
+                             f'lists have no definition for a third pass')
+        if self.model.cfg_mode == 'streams':
+            raise ValueError(f"flow_guidance = {s!r} together with cfg_mode = 'streams': the third pass is defined for cfg_mode = "
+                             f"'batched' only")
+        return float(s) - 1.
+
+    def _flow_network(self, x, t, classes, rgb_flow, mask, cond_scale, w):
+        """_network under flow_guidance: the passes with the no-flow one among them, then the shift, in place -> (cond logits,
+        null logits or None, computed-rows mask or None) for the code behind _network, unchanged"""
+        cond, null, uncond, computed = self.model._cond_null_noflow(x, t, classes, rgb_flow, mask, cond_scale)
+        ops.flow_guidance_shift(cond, null, uncond, w, keep=computed)
+        return cond, null, computed
+
+    # OPT-IN, 0. by default (nothing is drawn, loss and gradients are bit for bit what they are).  flow_drop_prob = p in [0, 1):
+    # training drops the flow condition of a sample with probability p — its normalised rgb_flow is +0.0, the no-flow pass's own
+    # input — so that a model learns the pass flow_guidance guides away from.  One (B,) uint8 draw by the route of Unet._keep_mask,
+    # directly after the noise draw and before the class-dropout draw; the photometric term keeps flow and mask as they are.
+    flow_drop_prob = 0.
+
+    def _check_flow_drop_prob(self):
+        p = self.flow_drop_prob
+        if not (isinstance(p, (int, float)) and not isinstance(p, bool) and 0. <= p < 1.):
+            raise ValueError(f'flow_drop_prob = {p!r}: a number in [0, 1)')
+        return float(p)
+
+    def _flow_keep(self, batch, device):
+        """the (batch,) uint8 draw of flow_drop_prob (1: the sample keeps its flow condition), or None at 0.: nothing drawn"""
+        return self.model._keep_mask(batch, self._check_flow_drop_prob(), device)
+
     def _network(self, x, t, classes, rgb_flow, mask, cond_scale, gate=None):
         """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null (``gate`` too)"""
         if cond_scale == 1:
@@ -396,6 +475,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         phi = self._rescale_phi(cond_scale)
         apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
         photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
+        fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
+        tag = {} if fg is None else {'flow': True}
         img = self.rng.randn(shape, device).contiguous()
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
@@ -403,7 +484,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         for k, (time, step, draws) in enumerate(steps):
             on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            if fg is None:
+                cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            else:                                            # the no-flow pass among the passes, and the shift in front of all else
+                cond, null, computed = self._flow_network(img, time_cond, classes, rgb_flow, mask, cond_scale, fg)
             noise = self.rng.randn(shape, device).contiguous() if draws else None
             more = {}
             if apg:                                          # the projected logits, then the update without a null pass
@@ -416,7 +500,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
                                                             trace is not None)
                 if trace is not None:
-                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra})
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra, **tag})
                 continue
             if rank is None:
                 img, x_start, _ = ops.sampler_step(step, cond, null, img, noise, want_x_start=trace is not None, keep=computed)
@@ -427,7 +511,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                                                     keep=computed)
             if trace is not None:
                 trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
-                              **more})
+                              **more, **tag})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -466,6 +550,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         phi = self._rescale_phi(cond_scale)
         apg = self._apg_on(cond_scale)                       # (refuses guidance_rescale and guidance_interval beside it)
         photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
+        fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
+        tag = {} if fg is None else {'flow': True}
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
@@ -474,7 +560,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         for k, (time, step, _) in enumerate(steps):
             on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            if fg is None:
+                cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
+            else:                                            # the no-flow pass among the passes, and the shift in front of all else
+                cond, null, computed = self._flow_network(img, time_cond, classes, rgb_flow, mask, cond_scale, fg)
             more = {}
             if apg:                                          # the projected logits, then the update without a null pass
                 cond, coef = self._apg_logits(step, cond, null, computed, apg, ast)
@@ -486,7 +575,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
                                                             trace is not None)
                 if trace is not None:
-                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra})
+                    trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **extra, **tag})
                 continue
             if rank is None:
                 img, x_start = ops.sampler_step_ms(step, cond, null, img, hist, want_x_start=trace is not None, keep=computed)
@@ -497,7 +586,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                                                     keep=computed)
             if trace is not None:
                 trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
-                              **more})
+                              **more, **tag})
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
         return img, mask, flow
 
@@ -545,7 +634,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         average, which fill zeroes on every call), and the launches behind them are those of cond_scale == 1 on the guided logits.
         With photo_guidance the update starts with dmh_photo_guide_dev on static buffers (flow and mask as fp32, the preconditioner
         s, the fixed-point accumulator, the guided logits): fill copies flow and mask and recomputes s on every call, the weight
-        is a launch argument and so part of the key."""
+        is a launch argument and so part of the key.  With flow_guidance the network is Unet._cond_null_noflow and
+        dmh_flow_guidance_shift stands in front of the update: no static buffer more, w = flow_guidance - 1 is a launch argument and
+        so part of the key."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
@@ -566,6 +657,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         photo = self._check_photo_guidance()                 # None: off.  (It refuses phi, apg_eta and an interval beside it.)
         if photo:
             key = key + (('photo', photo),)
+        fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
+        if fg is not None:                                   # (w is a launch argument of the shift: baked into the capture)
+            key = key + (('flow_guidance', fg),)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -599,6 +693,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             gate = (st['cursor'], st['guided']) if gated else None
 
             def network():                                   # -> the logits the update reads
+                if fg is not None:                           # the no-flow pass among the passes, the shift in front of all else
+                    return self._flow_network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale, fg)
                 if gate is None:
                     return self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale)
                 cond, null, computed = self._network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale, gate)
@@ -679,6 +775,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         noise = noise.to(torch.float32).contiguous()
         t = t.to(torch.int64).contiguous()
         x = self.q_sample(x_start, t, noise)
+        flow_keep = self._flow_keep(x_start.shape[0], x_start.device)    # flow_drop_prob: drawn behind the noise, before the class
+        if flow_keep is not None:                            # dropout.  (rgb_flow arrives normalised: 1 * v + 0 on kept rows)
+            rgb_flow = ops.affine_rows_keep(rgb_flow.to(torch.float32), 1., 0., flow_keep)
         model_out = self.model(x, t, classes, rgb_flow=rgb_flow, mask=mask)
         im1, im2 = model_out[:, :3].contiguous(), model_out[:, 3:].contiguous()
         im2_warp = flow_warp(im2, flow)

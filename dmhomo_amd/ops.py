@@ -5,6 +5,7 @@ pointers; every value is produced by a kernel of libdmhomo_hip.so.  Activations
 are NHWC fp32 tensors shaped (B, H, W, C).
 """
 import ctypes as C
+import math
 
 import os
 
@@ -891,6 +892,45 @@ def photo_energy(x, flow, mask, ws=None, out=None):
         raise ValueError(f'photo_energy: out {tuple(out.shape)} / ws of {ws.numel()} doubles for {B} x {H} x {W}')
     call('dmh_photo_energy', ptr(x), ptr(flow), ptr(mask), ptr(ws, torch.float64), ptr(out, torch.float64), B, H, W)
     return out
+
+
+def _keep_rows(who, keep, B):
+    if keep is not None and (tuple(keep.shape) != (B,) or keep.dtype != torch.uint8):
+        raise ValueError(f'{who}: keep {tuple(keep.shape)} {keep.dtype} for {B} rows (a (B,) uint8 mask)')
+
+
+def flow_guidance_shift(cond, null, uncond, w, keep=None):
+    """guidance on the flow condition, in place (dmh_flow_guidance_shift; the definition: include/dmhomo_hip.h): with the
+    no-flow logits ``uncond`` and w = flow_guidance - 1, e = w * (b - uncond) with b = ``null`` where there is a null pass, else
+    ``cond``; null += e and cond += e — but for the rows with keep == 0, which the conditional pass did not compute (``keep`` as
+    sampler_step, with null only).  It reads no DmhStep: the same call serves the eager and the replayed loop.  -> (cond, null)"""
+    B = cond.shape[0]
+    if tuple(uncond.shape) != tuple(cond.shape) or (null is not None and tuple(null.shape) != tuple(cond.shape)):
+        raise ValueError(f'flow_guidance_shift: uncond {tuple(uncond.shape)} / null {None if null is None else tuple(null.shape)} '
+                         f'against cond {tuple(cond.shape)}')
+    if keep is not None and null is None:
+        raise ValueError('flow_guidance_shift: keep without null (without a null pass every row of cond was computed)')
+    _keep_rows('flow_guidance_shift', keep, B)
+    w = float(w)
+    if not math.isfinite(w):
+        raise ValueError(f'flow_guidance_shift: w = {w!r} is not finite')
+    call('dmh_flow_guidance_shift', ptr(cond), ptr(null), ptr(uncond), ptr(keep, torch.uint8), w, B, cond.numel() // B)
+    return cond, null
+
+
+def affine_rows_keep(x, scale, shift, keep, out=None):
+    """affine with a keep bit per row (dmh_affine_rows_keep): out[b] = scale * x[b] + shift where keep[b] != 0, else +0.0 — the
+    normalisation of rgb_flow and the drop of ``flow_drop_prob`` in one launch.  keep: (B,) uint8."""
+    x = x.contiguous()
+    B = x.shape[0]
+    if keep is None:
+        raise ValueError('affine_rows_keep: keep is None (ops.affine is the call without a mask)')
+    _keep_rows('affine_rows_keep', keep, B)
+    y = torch.empty_like(x) if out is None else out
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f'affine_rows_keep: out {tuple(y.shape)} against x {tuple(x.shape)}')
+    call('dmh_affine_rows_keep', ptr(x), ptr(y), float(scale), float(shift), ptr(keep, torch.uint8), B, x.numel() // B)
+    return y
 
 
 def rng_indexed(shape, sample_ids, state, kind=0):

@@ -435,9 +435,12 @@ class TrainStep:
             self._sig = sig
 
     # ---- forward + backward of GaussianDiffusion.forward (CFG:808-842) on one 12-channel batch
-    def loss_and_grads(self, img, classes, t=None, noise=None, keep=None, grad_scale=1.0):
+    def loss_and_grads(self, img, classes, t=None, noise=None, keep=None, grad_scale=1.0, flow_keep=None):
         """-> (loss (0-dim tensor, unscaled), {parameter name: d(grad_scale * loss)/d parameter}).  ``t``, ``noise``,
-        ``keep`` default to the reference's draws, in its order (CFG:812 randint, CFG:773 randn_like, CFG:422 uniform)."""
+        ``keep`` default to the reference's draws, in its order (CFG:812 randint, CFG:773 randn_like, CFG:422 uniform).
+        ``flow_keep`` (B,) uint8: the samples that keep their flow condition; by default the draw of ``flow_drop_prob`` between
+        the noise and the class dropout (none at 0.).  A dropped sample's normalised rgb_flow is +0.0; flow and mask of the
+        photometric term stay (the stem input has no gradient: the backward kernels do not know about it)."""
         from .ddpm import flow_warp
         df = self.diffusion
         b, c, h, w = img.shape
@@ -448,11 +451,16 @@ class TrainStep:
             t = torch.randint(0, df.num_timesteps, (b,), device=dev).long()
         x_start = ops.affine(img[:, :6].to(torch.float32), 2., -1.)
         mask = img[:, 6:7].to(torch.float32).contiguous()
-        rgb_flow = ops.affine(img[:, -5:-2].to(torch.float32), 2., -1.)
         flow = img[:, -2:].to(torch.float32).contiguous()
         if noise is None:
             noise = df.rng.randn(x_start.shape, dev)
         noise = noise.to(torch.float32).contiguous()
+        if flow_keep is None:
+            flow_keep = df._flow_keep(b, dev)                # None at flow_drop_prob == 0.: nothing drawn
+        if flow_keep is None:
+            rgb_flow = ops.affine(img[:, -5:-2].to(torch.float32), 2., -1.)
+        else:
+            rgb_flow = ops.affine_rows_keep(img[:, -5:-2].to(torch.float32), 2., -1., flow_keep.to(torch.uint8).contiguous())
         t = t.to(torch.int64).contiguous()
         if keep is None:
             keep = self.unet._keep_mask(b, self.unet.cond_drop_prob, dev)

@@ -525,6 +525,37 @@ int dmh_photo_guide_dev(const DmhStep* cur_dev, const float* model_cond, const f
 int dmh_photo_energy(const float* x, const float* flow, const float* mask, double* ws, double* E, int B, int H, int W,
                      void* stream);
 
+/* Guidance on the homography condition, flow_guidance (not in the reference; the two-scale form of InstructPix2Pix, Brooks,
+ * Holynski, Efros 2023, with the flow in the image condition's place and the class in the text's).  The condition rgb_flow * mask
+ * enters the network through three stem channels only.  A "no-flow" pass is the network on the same x, time and mask with those
+ * three channels exactly +0.0.  flow_guidance = s_f is a finite number >= 0, w = s_f - 1 (computed on the host, passed as a
+ * float).  Per element i of row b (one sample: n = C*H*W):
+ *   case A, cond_scale != 1, three passes:  c = class kept by the drawn mask keep, with flow (the conditional pass);
+ *            n = null class, with flow (the null pass);  u = null class, no flow
+ *     e[i] = w * (n[i] - u[i])                                        fp32: the difference rounded, then the product
+ *     model_null[i] <- n[i] + e[i]
+ *     model_cond[i] <- c[i] + e[i]      on the rows the conditional pass computed (keep == NULL or keep[b] != 0); the other rows
+ *                                       of model_cond are neither read nor written
+ *   case B, cond_scale == 1, two passes:  c = the single pass with its class-dropout draw;  u = the SAME keep bits, no flow
+ *     e[i] = w * (c[i] - u[i]);   model_cond[i] <- c[i] + e[i]        = u + s_f * (c - u) in exact arithmetic
+ * In case A the blend of the step kernels, null' + (cond' - null') * s_c, is u + s_f * (n - u) + s_c * (c - n) in exact
+ * arithmetic, and cond' - null' is c - n up to rounding: the rescale, APG, the thresholds, the photometric correction and both
+ * samplers work on the shifted logits unchanged.  No random draw is added: the keep mask is drawn once, where it is drawn
+ * without the switch, and in case B it serves both passes.  w == 0 leaves every value (e is a zero), a sample whose stem
+ * channels are +0.0 already has n == u (c == u) bitwise and is left as it is.
+ *
+ * dmh_flow_guidance_shift: in place, one launch.  model_null != NULL: case A; model_null == NULL: case B, keep must be NULL.  It
+ * reads no DmhStep, so one entry serves the eager and the replayed loop.  16-byte loads and stores where model_cond, model_null
+ * and uncond meet 16-byte boundaries together (scalar head and tail; a vector that crosses a row boundary takes each element
+ * under its own row's keep bit), 4-byte words otherwise; a grid-stride loop, no LDS, no atomics: bitwise repeatable.  uncond must
+ * not overlap model_cond or model_null, model_cond not model_null; B >= 1, 1 <= n < 2^31, w finite.
+ * dmh_affine_rows_keep: y[i] = keep[b] != 0 ? x[i] * scale + shift : +0.0f — dmh_affine's arithmetic on kept rows (a dropped
+ * row's x is not read); the training side's normalisation of rgb_flow and the drop of flow_drop_prob in one launch.  y must not
+ * overlap x. */
+int dmh_flow_guidance_shift(float* model_cond, float* model_null, const float* uncond, const uint8_t* keep, float w, int B,
+                            int64_t n, void* stream);
+int dmh_affine_rows_keep(const float* x, float* y, float scale, float shift, const uint8_t* keep, int B, int64_t n, void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's training entry DGM/demo.py on dmhomo_amd.
 
-    python scripts/demo.py [-c <milestone>] [--data <CA-Homo Train dir>] [--steps N] [--image_size 256] [--bs 128] [--preview]
+    python scripts/demo.py [-c <milestone>] [--data <CA-Homo Train dir>] [--steps N] [--image_size 256] [--bs 128] [--preview] [--flow_drop_prob 0.1]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/demo.py ...
 
 Same model / diffusion / Trainer arguments as DEMO:15-58 (Unet dim 64, mults (1,2,4,8), 6 channels, 5 classes; l1,
@@ -12,7 +12,10 @@ pred_x0, 1000 steps; batch 128, lr 5e-4, accumulate 1, EMA 0.995).  Differences,
     conditions of dmhomo_amd.ddpm.SyntheticConditions are used;
   * --steps overrides the 112 500 steps of DEMO:34-45 so that a smoke run ends;
   * --preview turns on the sample sheets the reference always writes at every 1000th step (DDP:1871-1935:
-    results/sample-<m>-source.png / -target.png and a GIF); off by default.
+    results/sample-<m>-source.png / -target.png and a GIF); off by default;
+  * --flow_drop_prob P in [0, 1) drops the flow condition of a training sample with probability P (its rgb_flow channels of the
+    stem are zero), so that the model learns the no-flow pass that dgm_sample.py --flow_guidance guides away from (an addition;
+    GaussianDiffusion.flow_drop_prob); the default, 0, is the reference's training.
 """
 import argparse
 import os
@@ -31,6 +34,9 @@ parser.add_argument('--image_size', type=int, default=256)          # DEMO:24
 parser.add_argument('--bs', type=int, default=256 // 2)             # DEMO:34
 parser.add_argument('--results', type=str, default='results')
 parser.add_argument('--preview', action='store_true', help='write sample sheets at every save_and_sample_every-th step')
+parser.add_argument('--flow_drop_prob', type=float, default=0.,
+                    help='probability in [0, 1) of training a sample without its flow condition (not in the reference; '
+                         'GaussianDiffusion.flow_drop_prob); default: 0, never')
 args = parser.parse_args()
 
 num_classes = 5
@@ -41,6 +47,8 @@ def main():
     model = Unet(dim=64, dim_mults=(1, 2, 4, 8), channels=6, num_classes=num_classes).to(device)
     diffusion = GaussianDiffusion(model, image_size=args.image_size, timesteps=1000, sampling_timesteps=32, loss_type='l1',
                                   objective='pred_x0').to(device)
+    diffusion.flow_drop_prob = args.flow_drop_prob
+    diffusion._check_flow_drop_prob()
     D.broadcast_module_(diffusion, src=0)
     train_batch_size = args.bs
     data_num, epoch = 450000, 32

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -27,6 +27,11 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     loss, mask * (flow_warp(im2, flow) - im1) ** 2, by W * alpha_bar_t (photometric-consistency guidance; an addition), and
     prints each batch's mean dmhomo_amd.ddpm.photometric_error; the default, off, is the reference's sampler, which ignores the
     flow.  Not together with --guidance_rescale, --guidance_interval or --apg_eta;
+  * --flow_guidance S >= 0 guides on the homography condition itself (classifier-free guidance with two scales, as InstructPix2Pix;
+    an addition): every step also runs the network without rgb_flow and moves the logits by (S - 1) times the difference; 1 is
+    the unguided sampler at the cost of the extra pass, the default, off, is the reference's sampler.  It asks for a checkpoint
+    trained with demo.py --flow_drop_prob (otherwise the no-flow pass is out of distribution).  Not together with
+    --guidance_interval; the passes then run as one batched launch sequence (cfg_mode = 'batched');
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -93,6 +98,9 @@ parser.add_argument('--photo_guidance', type=float, default=None,
                     help='weight in (0, 1] of photometric-consistency guidance: every step moves its predicted pair towards '
                          'flow_warp(im2, flow) == im1 under the mask (not in the reference; GaussianDiffusion.photo_guidance); '
                          'default: off')
+parser.add_argument('--flow_guidance', type=float, default=None,
+                    help='scale >= 0 of classifier-free guidance on the flow condition: every step also runs a pass without '
+                         'rgb_flow (not in the reference; GaussianDiffusion.flow_guidance); default: off')
 args = parser.parse_args()
 
 num_classes = 1
@@ -126,6 +134,9 @@ def main():
     sampler.guidance_interval = None if args.guidance_interval is None else tuple(args.guidance_interval)
     sampler.apg_eta, sampler.apg_norm_threshold, sampler.apg_momentum = args.apg_eta, args.apg_norm_threshold, args.apg_momentum
     sampler.photo_guidance = args.photo_guidance
+    sampler.flow_guidance = args.flow_guidance
+    if args.flow_guidance is not None:
+        sampler.model.cfg_mode = 'batched'                 # the third pass rides in the one batched launch sequence
     trainer.score_photometric = args.photo_guidance is not None
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
