@@ -191,6 +191,8 @@ SIGNATURES = {
     'dmh_photo_energy': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, C.c_void_p]),
     'dmh_flow_guidance_shift': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, c_float, c_int, c_i64, C.c_void_p]),
     'dmh_affine_rows_keep': (c_int, [c_f32p, c_f32p, c_float, c_float, C.c_void_p, c_int, c_i64, C.c_void_p]),
+    'dmh_attention_pag': (c_int, [c_f32p, c_f32p, c_int, c_int, c_float, C.c_void_p, c_int, C.c_void_p]),
+    'dmh_pag_shift': (c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, c_float, c_int, c_i64, C.c_void_p]),
     'dmh_rng_indexed': (c_int, [c_f32p, c_int, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     'dmh_rng_keep_mask': (c_int, [C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_float, C.c_void_p]),
     'dmh_rows_lincomb': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i64, c_int, C.c_void_p]),

@@ -78,11 +78,12 @@ class Unet(nn.Module):
         return eng.stem(xin)
 
     def _run(self, x, time, classes, rgb_flow, mask, keeps, taps=None, x0=None, first=None, out=None, rows=None,
-             x0_per_pass=False):
+             x0_per_pass=False, pert_lo=None):
         """rows [rep*B + b]: sample b under class-keep mask keeps[rep] -> (len(keeps)*B, out_dim, H, W).
         first: engine.first_conv(x0) when the caller shares it between passes.
         rows: ``ops.rows_from_keep`` list of the rows to compute (the others stay unwritten), or None for all.
-        x0_per_pass: x0 holds the stem output of every pass already, len(keeps) * B rows (_cond_null_noflow)."""
+        x0_per_pass: x0 holds the stem output of every pass already, len(keeps) * B rows (_cond_null_noflow).
+        pert_lo: the rows >= pert_lo run mid_attn with the identity attention map (_cond_null_pag), or None for none."""
         eng = self._engine
         if x0 is None:
             x0 = self._stem(x, rgb_flow, mask)
@@ -100,9 +101,9 @@ class Unet(nn.Module):
             ss_all = torch.empty((len(keeps) * B, T.shape[1]), device=T.device, dtype=torch.float32)
             for r, k in enumerate(keeps):
                 ops.ss_gather(T, Ct, eng.mlp_b, cursor, classes, k, out=ss_all[r * B:(r + 1) * B])
-            return eng.trunk(x0, None, taps, first=first, out=out, ss_all=ss_all, rows=rows)
+            return eng.trunk(x0, None, taps, first=first, out=out, ss_all=ss_all, rows=rows, pert_lo=pert_lo)
         cond = eng.embed(time, [(classes, k) for k in keeps], len(keeps))
-        return eng.trunk(x0, cond, taps, first=first, out=out, rows=rows)
+        return eng.trunk(x0, cond, taps, first=first, out=out, rows=rows, pert_lo=pert_lo)
 
     def forward(self, x, time, classes, rgb_flow, mask, cond_drop_prob=None):
         cond_drop_prob = default(cond_drop_prob, self.cond_drop_prob)
@@ -187,6 +188,26 @@ class Unet(nn.Module):
         rows = ops.rows_from_keep(keep, extra=2 * B) if dedup else None
         three = self._run(None, time, classes, None, None, [keep, null, null], x0=torch.cat((x0, x0, x0u)), rows=rows,
                           x0_per_pass=True)
+        return three[:B], three[B:2 * B], three[2 * B:], (keep if dedup else None)
+
+    def _cond_null_pag(self, x, time, classes, rgb_flow, mask, cond_scale):
+        """the passes of GaussianDiffusion.pag_scale (include/dmhomo_hip.h has the definition): (cond logits, null logits or
+        None, perturbed logits, computed) as ONE launch sequence.  cond_scale != 1: 3B rows [c; n; p] — the two passes of
+        _cond_null and the conditional pass again with mid_attn's attention map replaced by the identity (pert_lo = 2B) — with
+        computed as _cond_null returns it; under dedup_dropped_rows every perturbed row is computed.  cond_scale == 1: 2B rows
+        [c; p] (pert_lo = B) with null and computed None.  The keep mask is drawn once, where _cond_null / forward draw it, and
+        serves c and p; the stem output is shared (row copies); every row is bitwise the row of a separate pass."""
+        if self.cfg_mode == 'streams':
+            raise ValueError("pag_scale with cfg_mode = 'streams': the perturbed pass is defined for cfg_mode = 'batched' only")
+        B = x.shape[0]
+        keep = self._keep_mask(B, self.cond_drop_prob, x.device)
+        if cond_scale == 1:
+            both = self._run(x, time, classes, rgb_flow, mask, [keep, keep], pert_lo=B)
+            return both[:B], None, both[B:], None
+        null = self._null_mask(B, x.device)
+        dedup = bool(self.dedup_dropped_rows) and keep is not None
+        rows = ops.rows_from_keep(keep, extra=2 * B) if dedup else None
+        three = self._run(x, time, classes, rgb_flow, mask, [keep, null, keep], rows=rows, pert_lo=2 * B)
         return three[:B], three[B:2 * B], three[2 * B:], (keep if dedup else None)
 
     # OPT-IN, off by default (bench.py's headline keeps it off and reports it under "variants").  The reference's conditional
@@ -411,6 +432,14 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         """the (batch,) uint8 draw of flow_drop_prob (1: the sample keeps its flow condition), or None at 0.: nothing drawn"""
         return self.model._keep_mask(batch, self._check_flow_drop_prob(), device)
 
+    def _pag_network(self, x, t, classes, rgb_flow, mask, cond_scale, s):
+        """_network under pag_scale (sampling.py: ScheduleHost.pag_scale): the passes with the perturbed one among them, then
+        the shift, in place -> (cond logits, null logits or None, computed-rows mask or None) for the code behind _network,
+        unchanged"""
+        cond, null, pert, computed = self.model._cond_null_pag(x, t, classes, rgb_flow, mask, cond_scale)
+        ops.pag_shift(cond, null, pert, s, keep=computed)
+        return cond, null, computed
+
     def _network(self, x, t, classes, rgb_flow, mask, cond_scale, gate=None):
         """-> (cond logits, null logits or None, computed-rows mask or None): see Unet._cond_null (``gate`` too)"""
         if cond_scale == 1:
@@ -477,6 +506,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
         fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
         tag = {} if fg is None else {'flow': True}
+        pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
+        if pg is not None:
+            tag = {'pag': True}
         img = self.rng.randn(shape, device).contiguous()
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
@@ -484,7 +516,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         for k, (time, step, draws) in enumerate(steps):
             on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            if fg is None:
+            if pg is not None:                               # the perturbed pass among the passes, the shift in front of all else
+                cond, null, computed = self._pag_network(img, time_cond, classes, rgb_flow, mask, cond_scale, pg)
+            elif fg is None:
                 cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
             else:                                            # the no-flow pass among the passes, and the shift in front of all else
                 cond, null, computed = self._flow_network(img, time_cond, classes, rgb_flow, mask, cond_scale, fg)
@@ -552,6 +586,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         photo = self._check_photo_guidance()                 # (refuses those two and apg_eta beside it)
         fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
         tag = {} if fg is None else {'flow': True}
+        pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
+        if pg is not None:
+            tag = {'pag': True}
         img = self.rng.randn(shape, device).contiguous()
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
@@ -560,7 +597,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         for k, (time, step, _) in enumerate(steps):
             on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
-            if fg is None:
+            if pg is not None:                               # the perturbed pass among the passes, the shift in front of all else
+                cond, null, computed = self._pag_network(img, time_cond, classes, rgb_flow, mask, cond_scale, pg)
+            elif fg is None:
                 cond, null, computed = self._network(img, time_cond, classes, rgb_flow, mask, cond_scale if on else 1)
             else:                                            # the no-flow pass among the passes, and the shift in front of all else
                 cond, null, computed = self._flow_network(img, time_cond, classes, rgb_flow, mask, cond_scale, fg)
@@ -636,7 +675,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         s, the fixed-point accumulator, the guided logits): fill copies flow and mask and recomputes s on every call, the weight
         is a launch argument and so part of the key.  With flow_guidance the network is Unet._cond_null_noflow and
         dmh_flow_guidance_shift stands in front of the update: no static buffer more, w = flow_guidance - 1 is a launch argument and
-        so part of the key."""
+        so part of the key.  With pag_scale the network is Unet._cond_null_pag and dmh_pag_shift stands in front of the update
+        in the same way: s = pag_scale is a launch argument and so part of the key."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
@@ -660,6 +700,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         fg = self._check_flow_guidance()                     # None: off, else w.  (It refuses an interval and 'streams'.)
         if fg is not None:                                   # (w is a launch argument of the shift: baked into the capture)
             key = key + (('flow_guidance', fg),)
+        pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
+        if pg is not None:                                   # (s is a launch argument of the shift: baked into the capture)
+            key = key + (('pag_scale', pg),)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -693,6 +736,8 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             gate = (st['cursor'], st['guided']) if gated else None
 
             def network():                                   # -> the logits the update reads
+                if pg is not None:                           # the perturbed pass among the passes, the shift in front of all else
+                    return self._pag_network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale, pg)
                 if fg is not None:                           # the no-flow pass among the passes, the shift in front of all else
                     return self._flow_network(st['img'], st['tcond'], ins[0], st['rf'], ins[2], cond_scale, fg)
                 if gate is None:

@@ -169,8 +169,13 @@ __global__ __launch_bounds__(256) void linattn_apply_kernel(const float* __restr
 // K4: softmax_j((q*scale)^T k) v, flash style with S^T = K Q^T so the softmax axis (keys) lies
 // on accumulator rows (registers + lane half) and P^T is already in B-operand position for
 // out^T[e][query] += V^T[e][key] P^T[key][query].  One wave per (sample, head, 32 queries).
+// PAG (dmh_attention_pag, perturbed-attention guidance): a wave whose physical row is >= pert_lo replaces the attention map by
+// the identity, so its output is v itself: lane (i, half) copies the 16 contiguous floats v[q0 + i][h*32 + 16*half ..] with
+// 16-byte loads and stores and retires before any q / k load.  The condition is uniform over the wave, and there is no barrier.
+template <bool PAG>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n,
-                                                        int qtiles, float scale, const int32_t* __restrict__ rows) {
+                                                        int qtiles, float scale, const int32_t* __restrict__ rows,
+                                                        int pert_lo) {
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int i = lane & 31, half = lane >> 5;
@@ -181,6 +186,16 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
   const int b = dmh_rows_phys(rows, bh >> 2);
   const float* base = qkv + (size_t)b * n * 384;
   const int q0 = qt * 32;
+  if (PAG && b >= pert_lo) {
+    const int qi = q0 + i;
+    if (qi < n) {
+      const float* vp = base + (size_t)qi * 384 + 256 + h * 32 + half * 16;
+      float* op = out + ((size_t)b * n + qi) * 128 + h * 32 + half * 16;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) st4(op + s4 * 4, ld4(vp + s4 * 4));
+    }
+    return;
+  }
 
   // B operand of S^T: q[query=i][d = 16*half + s] * scale
   float qf[16];
@@ -334,7 +349,21 @@ extern "C" int dmh_attention(const float* qkv, float* out, int B, int n, float s
   // query and key tiles of 32 (no export; tests/test_gpu_attn_core.py runs n = 31 ... 33, 63 ... 65 and 1025 around them)
   const int qtiles = cdiv(n, 32);
   const int waves = B * 4 * qtiles;  // always a multiple of 4: one workgroup = the 4 heads' waves in flight
-  hipLaunchKernelGGL(attention_kernel, dim3(waves / 4), dim3(256), 0, (hipStream_t)stream, qkv, out, n, qtiles, scale, rows);
+  hipLaunchKernelGGL(attention_kernel<false>, dim3(waves / 4), dim3(256), 0, (hipStream_t)stream, qkv, out, n, qtiles, scale,
+                     rows, 0);
   DMH_CHECK_LAUNCH("dmh_attention");
+  return DMH_OK;
+}
+
+// dmh_attention with perturbed rows (perturbed-attention guidance): physical rows >= pert_lo take the identity map, out = v
+extern "C" int dmh_attention_pag(const float* qkv, float* out, int B, int n, float scale, const int32_t* rows, int pert_lo,
+                                 void* stream) {
+  DMH_REQUIRE(qkv && out && B > 0 && n > 0, "dmh_attention_pag: bad arguments");
+  DMH_REQUIRE(pert_lo >= 0 && pert_lo <= B, "dmh_attention_pag: pert_lo=%d outside [0, B=%d]", pert_lo, B);
+  const int qtiles = cdiv(n, 32);
+  const int waves = B * 4 * qtiles;
+  hipLaunchKernelGGL(attention_kernel<true>, dim3(waves / 4), dim3(256), 0, (hipStream_t)stream, qkv, out, n, qtiles, scale,
+                     rows, pert_lo);
+  DMH_CHECK_LAUNCH("dmh_attention_pag");
   return DMH_OK;
 }

@@ -252,6 +252,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         if self._check_guidance_interval() is not None:
             raise ValueError('guidance_interval is not available in the unconditional class: it has no classifier-free guidance '
                              'to limit; use guidance_interval = None')
+        if self.pag_scale is not None:
+            raise ValueError('pag_scale is not available in the unconditional class: perturbed-attention guidance is built into '
+                             'the conditional sampler only; use pag_scale = None')
         if self._check_sampler() == 'dpmpp_2m':              # (walks the time list whatever is_ddim_sampling says)
             return self.dpmpp_sample(shape)
         return self.ddim_sample(shape) if self.is_ddim_sampling else self.p_sample_loop(shape)

@@ -39,6 +39,7 @@ class UnetEngine:
         self.groups = groups
         self._sig = None
         self._rows = None      # the active-row list of the trunk pass being launched (ops.rows_from_keep), or None
+        self._pert_lo = None   # perturbed-attention guidance: the rows >= it take mid_attn's identity map (trunk), or None
 
     # ------------------------------------------------------------------ weights
     def _signature(self):
@@ -184,7 +185,7 @@ class UnetEngine:
             o = ops.linear_attention_core(qkv, ATTN_SCALE, rows=rows)
             y = ops.conv2d(a.out, o, rows=rows)
             return ops.chan_layernorm(y, a.out_g, res=x, rows=rows)
-        o = ops.attention_core(qkv, ATTN_SCALE, rows=rows)
+        o = ops.attention_core(qkv, ATTN_SCALE, rows=rows, pert_lo=self._pert_lo)
         return ops.conv2d(a.out, o, res=x, rows=rows)
 
     # ------------------------------------------------------------------ program
@@ -239,21 +240,23 @@ class UnetEngine:
         self.ensure_prepared()
         return ops.conv2d(self.blocks[0][1].conv1, x0, None, want_stats=True)
 
-    def trunk(self, x0, cond, taps=None, first=None, out=None, ss_all=None, rows=None):
+    def trunk(self, x0, cond, taps=None, first=None, out=None, ss_all=None, rows=None, pert_lo=None):
         """everything after init_conv.  x0: stem() output with one row per row of ``cond``.
         first: ``first_conv(x0)`` when the caller has it already (shared between the CFG passes).
         out: a contiguous (rows, out_dim, H, W) tensor that receives the result (a row slice of the caller's buffer).
         ss_all: the (scale, shift) rows when the caller has them already (``ss_tables`` + ``ops.ss_gather``); ``cond`` is then unused.
         rows: the active-row list of this pass (``ops.rows_from_keep``): every launch works on the listed rows of its tensors
         only — the other rows of every intermediate and of the result stay unwritten (Unet.dedup_dropped_rows).
+        pert_lo: perturbed-attention guidance (include/dmhomo_hip.h): the rows >= pert_lo run the 'attn' member (mid_attn) with
+        the identity attention map (``ops.attention_core(..., pert_lo=)``); every other member does not know it.
         ``taps`` (dict) optionally receives the NHWC activation after each stage member, keyed like the
         reference's module names ('downs.0.0', 'mid_attn', ...): per-layer parity tests."""
         self.ensure_prepared()
-        self._rows = rows
+        self._rows, self._pert_lo = rows, pert_lo
         try:
             return self._trunk(x0, cond, taps, first, out, ss_all)
         finally:
-            self._rows = None
+            self._rows = self._pert_lo = None
 
     def _trunk(self, x0, cond, taps, first, out, ss_all):
         rows = self._rows

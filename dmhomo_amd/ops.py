@@ -319,12 +319,18 @@ def linear_attention_fused(x, ln_g, pla, scale, eps=1e-5, out=None, stats=None, 
     return o
 
 
-def attention_core(qkv, scale, rows=None):
-    """K4.  qkv (B,H,W,384) -> (B,H,W,128)."""
+def attention_core(qkv, scale, rows=None, pert_lo=None):
+    """K4.  qkv (B,H,W,384) -> (B,H,W,128).  pert_lo (perturbed-attention guidance, dmh_attention_pag): the physical rows
+    >= pert_lo take the identity attention map, their output is v = qkv[..., 256:]; None is dmh_attention as it is."""
     B, H, W, c = qkv.shape
     assert c == 384
     out = _empty((B, H, W, 128), qkv)
-    call('dmh_attention', ptr(qkv), ptr(out), B, H * W, float(scale), _rows(rows))
+    if pert_lo is None:
+        call('dmh_attention', ptr(qkv), ptr(out), B, H * W, float(scale), _rows(rows))
+        return out
+    if isinstance(pert_lo, bool) or not isinstance(pert_lo, int) or not 0 <= pert_lo <= B:
+        raise ValueError(f'attention_core: pert_lo = {pert_lo!r} for {B} rows (an int in [0, B])')
+    call('dmh_attention_pag', ptr(qkv), ptr(out), B, H * W, float(scale), _rows(rows), pert_lo)
     return out
 
 
@@ -915,6 +921,25 @@ def flow_guidance_shift(cond, null, uncond, w, keep=None):
     if not math.isfinite(w):
         raise ValueError(f'flow_guidance_shift: w = {w!r} is not finite')
     call('dmh_flow_guidance_shift', ptr(cond), ptr(null), ptr(uncond), ptr(keep, torch.uint8), w, B, cond.numel() // B)
+    return cond, null
+
+
+def pag_shift(cond, null, pert, s, keep=None):
+    """perturbed-attention guidance, in place (dmh_pag_shift; the definition: include/dmhomo_hip.h): with the logits ``pert`` of
+    the perturbed pass and s = pag_scale >= 0, e = s * (c - pert) with c = ``cond`` — on the rows with keep == 0, which the
+    conditional pass did not compute, ``null`` (``keep`` as sampler_step, with null only); null += e and cond += e on the
+    computed rows.  It reads no DmhStep: the same call serves the eager and the replayed loop.  -> (cond, null)"""
+    B = cond.shape[0]
+    if tuple(pert.shape) != tuple(cond.shape) or (null is not None and tuple(null.shape) != tuple(cond.shape)):
+        raise ValueError(f'pag_shift: pert {tuple(pert.shape)} / null {None if null is None else tuple(null.shape)} '
+                         f'against cond {tuple(cond.shape)}')
+    if keep is not None and null is None:
+        raise ValueError('pag_shift: keep without null (without a null pass every row of cond was computed)')
+    _keep_rows('pag_shift', keep, B)
+    s = float(s)
+    if not (math.isfinite(s) and s >= 0.):
+        raise ValueError(f'pag_shift: s = {s!r} is not a finite number >= 0')
+    call('dmh_pag_shift', ptr(cond), ptr(null), ptr(pert), ptr(keep, torch.uint8), s, B, cond.numel() // B)
     return cond, null
 
 

@@ -392,6 +392,41 @@ class ScheduleHost:
             raise ValueError(f'guidance_interval = {gi!r}: None, or a pair (lo, hi) of numbers with 0 <= lo <= hi <= 1')
         return float(gi[0]), float(gi[1])
 
+    # OPT-IN, None by default (every existing result, launch, RNG draw and graph key stays what it is).  pag_scale = s, a finite
+    # number >= 0: perturbed-attention guidance (Ahn et al. 2024, "Self-Rectifying Diffusion Sampling with Perturbed-Attention
+    # Guidance"; the reference has none) in the conditional class's sample().  It needs no label, no null class and no retraining:
+    # with the switch on the network also runs a perturbed pass p — the conditional pass with the attention map of mid_attn, the
+    # UNet's one full self-attention, replaced by the identity (dmh_attention_pag) — in the same launch sequence
+    # (Unet._cond_null_pag: 3B rows instead of 2B, resp. 2B instead of B), and dmh_pag_shift moves the logits by e = s * (c - p) in
+    # front of everything else: the blend behind it is n + cond_scale * (c - n) + s * (c - p) (include/dmhomo_hip.h has the
+    # definition; the update is linear, so it is the paper's formula under every objective).  guidance_rescale, apg_eta,
+    # photo_guidance, both clip modes, both samplers, every objective, dedup_dropped_rows and the captured step work on the shifted
+    # logits unchanged; no random draw is added (pag_scale = 0 gives the samples of None at the cost of the extra pass).  Refused
+    # with flow_guidance (a fourth pass is out of scope), with guidance_interval (the gated row lists have no definition for a
+    # third pass) and with cfg_mode = 'streams'.  The LinearAttention blocks are not perturbed.  model_predictions and
+    # forward_with_cond_scale do not know it.  What it does to samples of trained weights has not been measured.  The
+    # unconditional class refuses it (ddpm.GaussianDiffusion.sample).
+    pag_scale = None
+
+    def _check_pag(self):
+        """-> None (off), or s = pag_scale as a float"""
+        s = self.pag_scale
+        if s is None:
+            return None
+        if not (isinstance(s, (int, float)) and not isinstance(s, bool) and 0. <= s < float('inf')):
+            raise ValueError(f'pag_scale = {s!r}: None (off), or a finite number >= 0')
+        fg = getattr(self, 'flow_guidance', None)
+        if fg is not None:
+            raise ValueError(f'pag_scale = {s!r} together with flow_guidance = {fg!r}: a fourth pass is not defined; use one '
+                             f'of the two')
+        if self._check_guidance_interval() is not None:
+            raise ValueError(f'pag_scale = {s!r} together with guidance_interval = {self.guidance_interval!r}: the gated row '
+                             f'lists have no definition for a third pass')
+        if getattr(self.model, 'cfg_mode', None) == 'streams':
+            raise ValueError(f"pag_scale = {s!r} together with cfg_mode = 'streams': the perturbed pass is defined for cfg_mode "
+                             f"= 'batched' only")
+        return float(s)
+
     def _guided_entries(self, times, cond_scale):
         """which entries of a sampling loop over ``times`` are guided under guidance_interval: a list of bools, or None where
         the switch does nothing (no interval, or cond_scale == 1: no null pass to leave out) — the loops as they were"""

@@ -556,6 +556,39 @@ int dmh_flow_guidance_shift(float* model_cond, float* model_null, const float* u
                             int64_t n, void* stream);
 int dmh_affine_rows_keep(const float* x, float* y, float scale, float shift, const uint8_t* keep, int B, int64_t n, void* stream);
 
+/* Perturbed-attention guidance, pag_scale (not in the reference; Ahn et al. 2024, "Self-Rectifying Diffusion Sampling with
+ * Perturbed-Attention Guidance").  It needs no label, no null class and no retraining.
+ * The perturbed pass p is the conditional pass — same x, same time, same rgb_flow * mask, same class-keep bits — with one change:
+ * in mid_attn (the UNet's one full self-attention, K4) softmax(q k^T) is replaced by the identity matrix, so the attention
+ * core's output is v itself:
+ *     out[b][pix][h*32 + e] = qkv[b][pix][256 + h*32 + e]        exactly
+ * to_qkv, to_out, the pre-norm and the residual around it are unchanged, and so are the LinearAttention blocks (they have no
+ * attention map to replace).
+ * The shift, per element i of row b (one sample: n = C*H*W), with s = pag_scale >= 0, in fp32 without contraction:
+ *     c[i] = model_cond[i] where the conditional pass computed row b (keep == NULL or keep[b] != 0), else model_null[i]
+ *     d = c[i] - p[i] (rounded);   e = s * d (rounded)
+ *   case A, a null pass exists (cond_scale != 1):  model_null[i] <- model_null[i] + e
+ *                                                  model_cond[i] <- model_cond[i] + e   where row b was computed; the other rows
+ *                                                  of model_cond are neither read nor written
+ *   case B, no null pass (cond_scale == 1):        model_cond[i] <- c[i] + e
+ * In exact arithmetic the blend null' + (cond' - null') * cond_scale of the step kernels behind it is
+ * n + cond_scale * (c - n) + s * (c - p); no kernel behind the shift knows about it (flow_guidance uses the same trick), and
+ * because the update is linear it is the paper's epsilon-space formula under every objective.  s == 0 leaves every value (e is a
+ * zero), c == p leaves every value bitwise.  No random draw is added.
+ *
+ * dmh_attention_pag: dmh_attention in which every wave whose physical row b (behind the row list) is >= pert_lo takes the
+ * identity arm: lane (i, half) of the wave of (b, head h, queries q0 .. q0 + 31) copies the 16 floats v[q0 + i][h*32 + 16*half ..]
+ * with 16-byte loads and stores where q0 + i < n, and retires before any q / k load.  The condition is uniform over a wave and
+ * the kernel has no barrier.  0 <= pert_lo <= B; pert_lo == B perturbs nothing and is bitwise dmh_attention.
+ * dmh_pag_shift: in place, one launch.  model_null != NULL: case A; model_null == NULL: case B, keep must be NULL.  It reads no
+ * DmhStep, so one entry serves the eager and the replayed loop.  16-byte loads and stores where model_cond, model_null and pert
+ * meet 16-byte boundaries together (scalar head and tail; a vector that crosses a row boundary takes each element under its own
+ * row's keep bit), 4-byte words otherwise; a grid-stride loop, no LDS, no atomics: bitwise repeatable.  pert must not overlap
+ * model_cond or model_null, model_cond not model_null; B >= 1, 1 <= n < 2^31, s finite and >= 0. */
+int dmh_attention_pag(const float* qkv, float* out, int B, int n, float scale, const int32_t* rows, int pert_lo, void* stream);
+int dmh_pag_shift(float* model_cond, float* model_null, const float* pert, const uint8_t* keep, float s, int B, int64_t n,
+                  void* stream);
+
 /* Noise of the sampling loop keyed by GLOBAL sample index: replaces torch.randn(shape) CFG:679,
  * torch.randn_like(img) CFG:705 and torch.zeros(B).uniform_(0, 1) CFG:90 where a run is sharded over ranks.
  * out [B][per_sample]: element e of row b = f(seed, sample_ids[b], draw, e) with f = Philox4x32-10 (key = seed, counter =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -32,6 +32,11 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     the unguided sampler at the cost of the extra pass, the default, off, is the reference's sampler.  It asks for a checkpoint
     trained with demo.py --flow_drop_prob (otherwise the no-flow pass is out of distribution).  Not together with
     --guidance_interval; the passes then run as one batched launch sequence (cfg_mode = 'batched');
+  * --pag_scale S >= 0 turns on perturbed-attention guidance (Ahn et al. 2024; an addition): every step also runs the network
+    with the bottleneck self-attention map replaced by the identity and moves the logits by S times the difference to that
+    structurally degraded prediction; it needs no label and no retraining, so it works on any existing checkpoint; 0 is the
+    unguided sampler at the cost of the extra pass, the default, off, is the reference's sampler.  Not together with
+    --flow_guidance or --guidance_interval; the passes then run as one batched launch sequence (cfg_mode = 'batched');
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -101,6 +106,9 @@ parser.add_argument('--photo_guidance', type=float, default=None,
 parser.add_argument('--flow_guidance', type=float, default=None,
                     help='scale >= 0 of classifier-free guidance on the flow condition: every step also runs a pass without '
                          'rgb_flow (not in the reference; GaussianDiffusion.flow_guidance); default: off')
+parser.add_argument('--pag_scale', type=float, default=None,
+                    help='scale >= 0 of perturbed-attention guidance: every step also runs a pass whose bottleneck self-attention '
+                         'map is the identity (not in the reference; GaussianDiffusion.pag_scale); default: off')
 args = parser.parse_args()
 
 num_classes = 1
@@ -137,6 +145,9 @@ def main():
     sampler.flow_guidance = args.flow_guidance
     if args.flow_guidance is not None:
         sampler.model.cfg_mode = 'batched'                 # the third pass rides in the one batched launch sequence
+    sampler.pag_scale = args.pag_scale
+    if args.pag_scale is not None:
+        sampler.model.cfg_mode = 'batched'                 # the perturbed pass rides in the one batched launch sequence
     trainer.score_photometric = args.photo_guidance is not None
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
