@@ -343,7 +343,14 @@ def _ref_flow_warp(x, flow):
 @pytest.mark.parametrize('squared', [False, True], ids=['l1', 'l2'])
 def test_loss_backward_vs_autograd(ops, squared):
     """gradient of p_losses (CFG:796-806) wrt the UNet output, incl. the transpose of grid_sample; flows leave the
-    image on every side (border clamp) and fold over themselves"""
+    image on every side (border clamp) and fold over themselves.  Two references, one bound: float64 autograd through a
+    float64 warp (the assertion this test has always made), and the float64 statement of tests/aux_cases.py, which takes the
+    kernel's own fp32 ``warped`` as given, as the kernel's contract does.  For L1 the first is sound only while no
+    |warped - im1| lies below the warp's rounding error: there the two warps disagree on sign(warped - im1) and autograd
+    is 2 n2 away from any kernel (tests/test_aux_host.py shows it on a planted tie).  At this seed the smallest
+    |warped - im1| is printed and asserted to be above 1e-6, so the assertion stays for L1 as well; the second reference
+    has no such condition."""
+    import aux_cases as ax
     B, H, W = 3, 24, 40
     out = rand((B, 6, H, W), 800)
     target = rand((B, 6, H, W), 801)
@@ -360,6 +367,13 @@ def test_loss_backward_vs_autograd(ops, squared):
     warped = ops.flow_warp(o[:, 3:].contiguous(), flow.to(dev()))
     got = ops.loss_backward(o, target.to(dev()), warped, mask.to(dev()), flow.to(dev()), abar.to(dev()), squared)
     assert _rel('loss backward', got, gref) < 5e-6
+    inp = dict(out=out, target=target, warped=warped.cpu(), mask=mask, flow=flow, abar=abar)
+    tie = (inp['warped'].double() - out[:, :3].double()).abs().min().item()
+    print(f'[parity] loss backward: min |warped - im1| = {tie:.3e}')
+    assert tie > 1e-6
+    st = ax.lb_statement(inp, squared, torch.float64)['dout']
+    assert _rel('loss backward vs the statement on the fp32 warped, dout[:, :3]', got[:, :3], st[:, :3]) < 5e-6
+    assert _rel('loss backward vs the statement on the fp32 warped, dout[:, 3:]', got[:, 3:], st[:, 3:]) < 5e-6
 
 
 def test_adam_clip_ema_vs_torch(ops):

@@ -18,6 +18,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from aux_cases import adam_step64, ulp32_spacing as _ulp32     # shared with the single-tensor entries (tests/test_gpu_aux.py)
+
 pytestmark = pytest.mark.gpu
 
 TH, TW = 4, 16                  # pixels of an item (a 4 x 16 tile of dy)
@@ -406,12 +408,6 @@ def test_linear_backward_vs_fp64(ops, cout, cin, Bn):
         assert e[0] <= 2e-6 and e[1] <= 1.2e-6 and e[2] <= 5e-7, e
 
 
-def _ulp32(a):
-    """spacing of fp32 numbers at |a| (fp64 tensor); 2^-149 below the normal range"""
-    a = a.abs().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(a)) - 23)
-
-
 def _act_inputs():
     x = torch.cat([torch.linspace(-100, 100, 200001), torch.linspace(-95, -80, 3001), torch.linspace(-16, 4, 4001),
                    torch.tensor([0.0, -0.0, 1e-45, -1e-45, 1e-40, -1e-40, 1.1e-38, -1.1e-38, 2.0 ** -126, -2.0 ** -126,
@@ -516,7 +512,6 @@ def test_clip_adam_multi_vs_fp64(ops, max_norm):
     max(|p|, |step|) for p (the sums cancel where the terms have opposite signs)"""
     sizes = [1, 4095, 4096, 4097, 3 * 4096 + 5] * 10 + [4097, 1, 4096]
     lr, b1, b2, eps = 1e-3, 0.9, 0.99, 1e-8
-    f1, f2 = float(torch.tensor(b1)), float(torch.tensor(b2))          # the betas as fp32 values
     g = torch.Generator().manual_seed(123)
     p0 = [torch.randn(n, generator=g) for n in sizes]
     P = [t.to(_dev()) for t in p0]
@@ -531,18 +526,10 @@ def test_clip_adam_multi_vs_fp64(ops, max_norm):
         nrm = torch.sqrt(sum((t.double() ** 2).sum() for t in gs))
         coef = min(1.0, max_norm / (nrm.item() + 1e-6))
         assert (coef < 1.0) == (max_norm == 1.0)
-        bc1, bc2 = 1 - f1 ** step, 1 - f2 ** step
         c = clip.cpu().double()
         worst['norm'] = max(worst['norm'], abs(c[0].item() - nrm.item()) / nrm.item(), abs(c[1].item() - coef) / coef)
         for i, gr in enumerate(gs):
-            gd = gr.double() * c[1].item()
-            sm = torch.maximum((f1 * rm[i]).abs(), ((1 - f1) * gd).abs())
-            sv = torch.maximum(f2 * rv[i], (1 - f2) * gd * gd)
-            rm[i] = f1 * rm[i] + (1 - f1) * gd
-            rv[i] = f2 * rv[i] + (1 - f2) * gd * gd
-            upd = (lr / bc1) * (rm[i] / (rv[i].sqrt() / bc2 ** 0.5 + eps))
-            sp = torch.maximum(rp[i].abs(), upd.abs())
-            rp[i] = rp[i] - upd
+            (rp[i], rm[i], rv[i]), (sp, sm, sv) = adam_step64(rp[i], rm[i], rv[i], gr, c[1].item(), step, lr, b1, b2, eps)
             for key, got, want, sc in (('p', P[i], rp[i], sp), ('m', M[i], rm[i], sm), ('v', V[i], rv[i], sv)):
                 worst[key] = max(worst[key], ((got.cpu().double() - want).abs() / _ulp32(sc)).max().item())
             rp[i], rm[i], rv[i] = P[i].cpu().double(), M[i].cpu().double(), V[i].cpu().double()   # next step from the kernel's state
