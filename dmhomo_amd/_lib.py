@@ -220,6 +220,15 @@ SIGNATURES = {
     'dmh_hem_flow': (c_int, [C.c_void_p, c_int, c_int, c_int, c_f32p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); the entries include/dmhomo_hip_known.h declares: the same library and error channel, a table of
+# their own (SIGNATURES is the table of dmhomo_hip.h, whose version stays what it is)
+EXTENSIONS = {
+    'dmh_known_blend': (c_int, [c_f32p, c_f32p, C.c_void_p, c_float, c_f32p, C.c_void_p, c_f32p, c_int, c_i64, C.c_void_p]),
+    'dmh_known_error_splits': (c_int, [c_int, c_i64]),
+    'dmh_known_error': (c_int, [c_f32p, c_f32p, C.c_void_p, c_float, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_i64,
+                                C.c_void_p]),
+}
+
 DLT_BLOCKS = 64
 
 _lib = None
@@ -237,8 +246,8 @@ def lib():
             raise DmhError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            f'or `make -C dmhomo_amd/csrc` — dmhomo_amd has no CPU / eager fallback')
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)          # AttributeError if the symbol is missing
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSIONS.items()):
+            fn = getattr(h, name)          # AttributeError if the symbol is missing (a stale library fails here, loudly)
             fn.restype = res
             fn.argtypes = args
         got = int(h.dmh_version())

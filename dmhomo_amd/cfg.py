@@ -379,6 +379,55 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         return ops.photo_guide(step, cond, null, computed, pst['flow'], pst['mask'], pst['s'], w, pst['acc'],
                                out=pst['guided']), more
 
+    # ---- known pixels (sample_known; sampling.py: ScheduleHost.known_resample has the description, include/dmhomo_hip_known.h
+    # the definition)
+    KNOWN_MASKS = {'source': (0, 3), 'target': (3, 6)}
+
+    def _known_inputs(self, known, known_mask, shape):
+        """the checks of a sample_known call, once per call -> {'known': (B, 6, H, W) fp32 in [0, 1], 'mask': (B, 6 H W) uint8,
+        'stays': known_resample - 1, 'score': bool(score_known)}, what the loops take as ``known``"""
+        stays = self._check_known()
+        device = self.betas.device
+        if not torch.is_tensor(known) or tuple(known.shape) != tuple(shape):
+            raise ValueError(f'sample_known: known {tuple(known.shape) if torch.is_tensor(known) else type(known).__name__} '
+                             f'against the image pair {tuple(shape)}')
+        known = known.to(device=device, dtype=torch.float32).contiguous()
+        if not bool(((known >= 0.) & (known <= 1.)).all()):  # (a NaN fails both comparisons)
+            raise ValueError('sample_known: known has values outside [0, 1], the range of the sampler\'s output and of the '
+                             'dataset\'s image channels')
+        if isinstance(known_mask, str):
+            if known_mask not in self.KNOWN_MASKS:
+                raise ValueError(f'sample_known: known_mask = {known_mask!r}: a tensor, or one of {tuple(self.KNOWN_MASKS)}')
+            lo, hi = self.KNOWN_MASKS[known_mask]
+            kmask = torch.zeros(shape, device=device, dtype=torch.uint8)
+            kmask[:, lo:hi] = 1
+        else:
+            try:
+                kmask = (torch.as_tensor(known_mask).to(device) != 0).to(torch.uint8).expand(shape).contiguous()
+            except (RuntimeError, TypeError) as e:
+                raise ValueError(f'sample_known: known_mask does not broadcast to {tuple(shape)}: {e}') from None
+        return {'known': known, 'mask': kmask.reshape(shape[0], -1), 'stays': stays, 'score': bool(self.score_known)}
+
+    @staticmethod
+    def _known_state(known, shape, device):
+        """the buffers one eager loop keeps: K = 2 * known - 1, the overwritten logits, the score's fp64 workspace"""
+        K = ops.affine(known['known'], 2., -1.)
+        return {'K': K, 'logits': torch.empty(shape, device=device, dtype=torch.float32), 'ws': ops.known_error_workspace(K)}
+
+    @staticmethod
+    def _known_logits(cond, null, computed, cond_scale, known, kst, k, n_entries, tracing):
+        """one eager step's logits with the kept elements in them -> (logits, what the trace adds); the update behind it takes
+        (logits, None, keep=None).  The score of the entry's own logits first: on the last entry with score_known (it stays in
+        ``known['err']``), on every entry when tracing"""
+        cs = cond_scale if null is not None else 1.
+        more = {}
+        if tracing or (known['score'] and k == n_entries - 1):
+            err = ops.known_error(cond, null, computed, cs, kst['K'], known['mask'], ws=kst['ws'])
+            more['known_err'] = err
+            if k == n_entries - 1:
+                known['err'] = err
+        return ops.known_blend(cond, null, computed, cs, kst['K'], known['mask'], out=kst['logits']), more
+
     # OPT-IN, None by default (every existing result, launch, RNG draw and graph key stays what it is).  flow_guidance = s_f, a
     # finite number >= 0: classifier-free guidance on the homography condition in sample() — the label of this data set sits in
     # rgb_flow * mask (the class is always 0, DDP:1136), which reaches the network through three stem channels only.  With the switch
@@ -492,13 +541,15 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         """CFG:669-711."""
         return self._ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale, clip_denoised)
 
-    def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
+    def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
         'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac' at the guided entries; 'guided': whether
         the entry ran with the null pass, False only under guidance_interval; with apg_eta, the step's (A, Cc) per row, 'apg' (B, 2);
-        with photo_guidance, the photometric energy of the blend before the correction, 'photo' (B,) float64)."""
+        with photo_guidance, the photometric energy of the blend before the correction, 'photo' (B,) float64; with ``known``, the
+        score of the entry's logits 'known_err' (B,) float64, and 'stay': True on the stay entries of known_resample).
+        known: what _known_inputs returns (sample_known), or None: the loop as it was."""
         batch, device = shape[0], self.betas.device
-        steps = self._ddim_steps(clip_denoised, cond_scale)
+        steps = self._ddim_steps(clip_denoised, cond_scale, known['stays'] if known else 0)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
@@ -513,6 +564,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
         pst = self._photo_state(shape, flow, mask, device) if photo else None
+        kst = self._known_state(known, shape, device) if known else None
         for k, (time, step, draws) in enumerate(steps):
             on = guided is None or guided[k]                 # (an unguided entry: the entry at cond_scale == 1, no null pass)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
@@ -530,6 +582,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if photo:                                        # the corrected logits, then the update without a null pass
                 cond, more = self._photo_logits(step, cond, null, computed, photo, pst, cond_scale, trace is not None)
                 null, computed = None, None
+            if known:                                        # the kept elements over the logits, then the update without a null pass
+                cond, kmore = self._known_logits(cond, null, computed, cond_scale, known, kst, k, len(steps), trace is not None)
+                null, computed, more = None, None, {**more, **kmore}
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, noise, None, rank, phi, ws,
                                                             trace is not None)
@@ -546,7 +601,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if trace is not None:
                 trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
                               **more, **tag})
+                if known and known['stays'] and k % (known['stays'] + 1) != known['stays']:
+                    trace[-1]['stay'] = True
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
+        if known:                                            # the kept elements come back as the caller gave them, bit for bit
+            ops.known_blend(img, None, None, 1., known['known'], known['mask'])
         return img, mask, flow
 
     def _dynamic_rank(self, shape, clip):
@@ -573,10 +632,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                                            keep=computed)
         return img, x_start, {'gfac': gfac, **({} if thr is None else {'thr': thr})}
 
-    def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None):
+    def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None):
         """the loop of _ddim_sample with the multistep solver's update (ScheduleHost._dpmpp_steps; not in the reference): the
         network call — its class-dropout draw included — is the same, the update draws nothing and carries the previous step's
-        x_start in ``hist``.  ``trace`` as _ddim_sample."""
+        x_start in ``hist``.  ``trace`` and ``known`` as _ddim_sample (no stay entries: _check_known)."""
         batch, device = shape[0], self.betas.device
         steps = self._dpmpp_steps(clip_denoised, cond_scale)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
@@ -594,6 +653,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
         pst = self._photo_state(shape, flow, mask, device) if photo else None
+        kst = self._known_state(known, shape, device) if known else None
         for k, (time, step, _) in enumerate(steps):
             on = guided is None or guided[k]                 # (the history carries across guided / unguided entries unchanged)
             time_cond = torch.full((batch,), time, device=device, dtype=torch.long)
@@ -610,6 +670,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if photo:                                        # the corrected logits, then the update without a null pass
                 cond, more = self._photo_logits(step, cond, null, computed, photo, pst, cond_scale, trace is not None)
                 null, computed = None, None
+            if known:                                        # the kept elements over the logits, then the update without a null pass
+                cond, kmore = self._known_logits(cond, null, computed, cond_scale, known, kst, k, len(steps), trace is not None)
+                null, computed, more = None, None, {**more, **kmore}
             if phi and on:
                 img, x_start, extra = self._rescaled_update(step, cond, null, computed, img, None, hist, rank, phi, ws,
                                                             trace is not None)
@@ -626,7 +689,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             if trace is not None:
                 trace.append({'time': time, 'x_start': x_start, 'img': img, 'guided': on, **({} if thr is None else {'thr': thr}),
                               **more, **tag})
+                if known and known['stays'] and k % (known['stays'] + 1) != known['stays']:
+                    trace[-1]['stay'] = True
         img = ops.affine(img, 0.5, 0.5)                      # unnormalize_to_zero_to_one, CFG:709
+        if known:                                            # the kept elements come back as the caller gave them, bit for bit
+            ops.known_blend(img, None, None, 1., known['known'], known['mask'])
         return img, mask, flow
 
     @torch.no_grad()
@@ -653,13 +720,35 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             return self._dpmpp_sample(classes, rgb_flow, flow, mask, shape, cond_scale)
         return self.ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale)
 
-    def _graph_tables(self, cond_scale, clip=True):
+    @torch.no_grad()
+    def sample_known(self, known, known_mask, classes, rgb_flow, flow, mask, cond_scale=3.):
+        """sample() around known pixels (not in the reference; sampling.py: ScheduleHost.known_resample has the description):
+        known (B, 6, H, W) fp32 in [0, 1]; known_mask anything that broadcasts to it (nonzero: keep this element), or 'source'
+        (channels 0-2) / 'target' (channels 3-5).  -> (img, mask, flow) like sample, the kept elements of img bit for bit those
+        of ``known``.  With score_known the call leaves last_known_error (B,) float64."""
+        batch_size, image_size, channels = classes.shape[0], self.image_size, self.channels
+        shape = (batch_size, channels, image_size, image_size)
+        kn = self._known_inputs(known, known_mask, shape)
+        solver = self._check_sampler() == 'dpmpp_2m'
+        if not self.is_ddim_sampling and not solver:
+            return self.p_sample_loop(classes, rgb_flow, flow, mask, shape, cond_scale)    # TypeError, as sample()
+        if self.hip_graph and type(self.rng) is DeviceRng and self.sampling_timesteps >= 1:
+            out = self._sample_graphed(classes, rgb_flow, flow, mask, shape, cond_scale, known=kn)
+        else:
+            rgb_flow = ops.affine(rgb_flow.to(torch.float32), 2., -1.)      # normalize_to_neg_one_to_one, CFG:716
+            loop = self._dpmpp_sample if solver else self._ddim_sample
+            out = loop(classes, rgb_flow, flow, mask, shape, cond_scale, known=kn)
+        if kn['score']:
+            self.last_known_error = kn['err']
+        return out
+
+    def _graph_tables(self, cond_scale, clip=True, stays=0):
         """host side of the replayed loop: (steps, times, draws), entry k = the DmhStep, timestep and 'draws noise' flag
-        _ddim_sample (or, with sampler = 'dpmpp_2m', _dpmpp_sample) passes at its k-th step."""
-        times, steps, draws = map(list, zip(*self._sampler_steps(clip, cond_scale)))
+        _ddim_sample (or, with sampler = 'dpmpp_2m', _dpmpp_sample) passes at its k-th step (stays: sample_known's stay entries)."""
+        times, steps, draws = map(list, zip(*self._sampler_steps(clip, cond_scale, stays)))
         return steps, times, draws
 
-    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale):
+    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale, known=None):
         """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times.
         With sampler = 'dpmpp_2m' the step is the network, dmh_sampler_step_ms_dev on a static history buffer and the seek:
         no randn launch is left in it.  With clip_mode = 'dynamic' the update is two calls, dmh_sampler_threshold_dev and
@@ -676,7 +765,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         is a launch argument and so part of the key.  With flow_guidance the network is Unet._cond_null_noflow and
         dmh_flow_guidance_shift stands in front of the update: no static buffer more, w = flow_guidance - 1 is a launch argument and
         so part of the key.  With pag_scale the network is Unet._cond_null_pag and dmh_pag_shift stands in front of the update
-        in the same way: s = pag_scale is a launch argument and so part of the key."""
+        in the same way: s = pag_scale is a launch argument and so part of the key.  With ``known`` (sample_known) dmh_known_blend stands
+        between those and the update on static buffers (K, known, the expanded mask, the overwritten logits; with score_known the
+        fp64 workspace and the result, written by dmh_known_error in the last step only): fill copies this call's known and mask,
+        whose values are not part of the key — only that the feature is on, known_resample and score_known are —, the stay entries
+        are entries of the step table, and last() ends with the unnormalise and the write-back."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
@@ -703,6 +796,9 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
         if pg is not None:                                   # (s is a launch argument of the shift: baked into the capture)
             key = key + (('pag_scale', pg),)
+        stays = known['stays'] if known else 0
+        if known:                                            # (the table's length and the score's launches: baked in; the pixels not)
+            key = key + (('known', stays + 1, known['score']),)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -733,6 +829,14 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 st['photo_acc'] = ops.photo_acc(shape[0], shape[2], shape[3], device)
                 st['photo_s'] = ops.photo_weights(st['photo_flow'], st['photo_mask'], st['photo_acc'])
                 st['photo_guided'] = torch.zeros(shape, device=device)
+            if known:                                        # known pixels: K, known, the mask (nothing kept until fill writes it),
+                st['known_K'] = torch.zeros(shape, device=device)            # the overwritten logits, the score's buffers
+                st['known_01'] = torch.zeros(shape, device=device)
+                st['known_mask'] = torch.zeros((shape[0], shape[1] * shape[2] * shape[3]), device=device, dtype=torch.uint8)
+                st['known_logits'] = torch.zeros(shape, device=device)
+                if known['score']:
+                    st['known_ws'] = ops.known_error_workspace(st['img'])
+                    st['known_err'] = torch.zeros((shape[0],), device=device, dtype=torch.float64)
             gate = (st['cursor'], st['guided']) if gated else None
 
             def network():                                   # -> the logits the update reads
@@ -746,7 +850,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 ops.guidance_gate(*gate, cond, null)         # an unguided entry: null <- cond, the update below is the unguided one
                 return cond, null, computed
 
-            def step(cond, null, computed, noise, out):      # the update of the entry at the cursor
+            def step(cond, null, computed, noise, out, final=False):     # the update of the entry at the cursor
                 hist = st['hist'] if solver else None
                 if apg:                                      # the projected logits, then the update without a null pass
                     ops.apg_coef_dev(st['cur'], cond, null, *apg, keep=computed, run=st['apg_run'], ws=st['apg_ws'],
@@ -756,6 +860,13 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 if photo:                                    # the corrected logits, then the update without a null pass
                     cond = ops.photo_guide_dev(st['cur'], cond, null, computed, st['photo_flow'], st['photo_mask'], st['photo_s'],
                                                photo, st['photo_acc'], out=st['photo_guided'])
+                    null = computed = None
+                if known:                                    # the kept elements over the logits, then the update without a null pass
+                    cs = cond_scale if null is not None else 1.
+                    if final and known['score']:             # the score of the last entry's own logits
+                        ops.known_error(cond, null, computed, cs, st['known_K'], st['known_mask'], ws=st['known_ws'],
+                                        out=st['known_err'])
+                    cond = ops.known_blend(cond, null, computed, cs, st['known_K'], st['known_mask'], out=st['known_logits'])
                     null = computed = None
                 if phi:
                     ops.guidance_factor_dev(st['cur'], cond, null, phi, keep=computed, ws=st['gws'], gfac=st['gfac'])
@@ -780,7 +891,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
 
             def last():                                      # CFG:693-695 + unnormalize, CFG:709
                 logits = network()
-                return ops.affine(step(*logits, None, None), 0.5, 0.5)
+                out = ops.affine(step(*logits, None, None, final=True), 0.5, 0.5)
+                if known:                                    # the kept elements come back as the caller gave them, bit for bit
+                    ops.known_blend(out, None, None, 1., st['known_01'], st['known_mask'])
+                return out
             return mid, last
 
         def fill(st):
@@ -794,10 +908,16 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 st['photo_flow'].copy_(flow)
                 st['photo_mask'].copy_(mask)
                 ops.photo_weights(st['photo_flow'], st['photo_mask'], st['photo_acc'], out=st['photo_s'])
+            if known:                                        # this call's pixels and mask
+                st['known_01'].copy_(known['known'])
+                ops.affine(st['known_01'], 2., -1., out=st['known_K'])
+                st['known_mask'].copy_(known['mask'])
             if gated:
-                flags = self._guided_entries(self._graph_tables(cond_scale, clip)[1], cond_scale)
+                flags = self._guided_entries(self._graph_tables(cond_scale, clip, stays)[1], cond_scale)
                 st['guided'].copy_(torch.tensor(flags, dtype=torch.uint8))
-        img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip), buffers, fill)
+        img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip, stays), buffers, fill)
+        if known and known['score']:
+            known['err'] = self.__dict__['_graph_state']['known_err'].clone()
         return img, mask, flow
 
     @torch.no_grad()

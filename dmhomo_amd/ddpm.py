@@ -612,11 +612,20 @@ class Trainer(object):
     ``save_and_sample_every``-th step (DDP:1871-1935), ``sample`` at every 100th ``step`` (DDP:1972-2019).
 
     ``score_photometric`` (class attribute, off by default): ``sample`` also leaves ``photometric_error`` of the batch it drew,
-    (B,) float64, in ``last_photometric_error``; the record returned is the same either way."""
+    (B,) float64, in ``last_photometric_error``; the record returned is the same either way.
+
+    ``keep`` (class attribute, None by default): 'source' or 'target' — ``sample`` keeps that image of the batch's own pair
+    (channels 0-5 of every dataset batch are img1 | img2) and generates only the other one around it, through
+    ``sample_known`` of the conditional sampler; the kept image's bytes in the record are the batch's.  The record format is
+    unchanged.  ``score_known`` (off by default): with ``keep``, the call also leaves the sampler's ``last_known_error``, (B,)
+    float64, in ``last_known_error``."""
 
     preview = False
     score_photometric = False
     last_photometric_error = None
+    keep = None
+    score_known = False
+    last_known_error = None
 
     def __init__(self, diffusion_model, folder, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_horizontal_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10,
@@ -772,8 +781,26 @@ class Trainer(object):
         rgb_flows = data[0][:, -5:-2].to(dev)
         flows = data[0][:, -2:].to(dev).contiguous()
         mask = data[0][:, -6:-5].to(dev)
-        with torch.no_grad():
-            all_images = self.ema.ema_model.sample(classes=data[1].to(dev), rgb_flow=rgb_flows, flow=flows, mask=mask)
+        if self.keep is not None:
+            if self.keep not in ('source', 'target'):
+                raise ValueError(f"Trainer.keep = {self.keep!r}: None, 'source' or 'target'")
+            sampler = self.ema.ema_model
+            if not hasattr(sampler, 'sample_known'):
+                raise ValueError(f'Trainer.keep = {self.keep!r}: {type(sampler).__module__}.{type(sampler).__name__} has no '
+                                 f'sample_known (the conditional sampler has)')
+            was = sampler.score_known
+            sampler.score_known = bool(self.score_known) or was
+            try:
+                with torch.no_grad():
+                    all_images = sampler.sample_known(data[0][:, :6].to(dev), self.keep, classes=data[1].to(dev),
+                                                      rgb_flow=rgb_flows, flow=flows, mask=mask)
+            finally:
+                sampler.score_known = was
+            if self.score_known:
+                self.last_known_error = sampler.last_known_error
+        else:
+            with torch.no_grad():
+                all_images = self.ema.ema_model.sample(classes=data[1].to(dev), rgb_flow=rgb_flows, flow=flows, mask=mask)
         ret = saveTrainPair(all_images[0], mask=all_images[1], flows=all_images[2])
         if self.score_photometric:
             self.last_photometric_error = photometric_error(all_images[0], all_images[2], all_images[1])

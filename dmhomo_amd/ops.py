@@ -943,6 +943,76 @@ def pag_shift(cond, null, pert, s, keep=None):
     return cond, null
 
 
+def _known_shapes(who, model_cond, model_null, keep, known, kmask):
+    """-> (B, per_row) of the known-pixel calls: known as model_cond, kmask one uint8 per element of it"""
+    shape = tuple(model_cond.shape)
+    if model_cond.dim() < 2 or (model_null is not None and tuple(model_null.shape) != shape) or tuple(known.shape) != shape:
+        raise ValueError(f'{who}: known {tuple(known.shape)} / null {None if model_null is None else tuple(model_null.shape)} '
+                         f'against model_cond {shape}')
+    if kmask.dtype != torch.uint8 or kmask.numel() != model_cond.numel() or kmask.shape[0] != shape[0]:
+        raise ValueError(f'{who}: kmask {tuple(kmask.shape)} {kmask.dtype} against model_cond {shape} (one uint8 per element, row '
+                         f'by row)')
+    if keep is not None and model_null is None:
+        raise ValueError(f'{who}: keep without null (without a null pass every row of cond was computed)')
+    _keep_rows(who, keep, shape[0])
+    return shape[0], model_cond.numel() // shape[0]
+
+
+def _aliases(a, b):
+    return b is not None and a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and \
+        b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
+
+
+def known_blend(model_cond, model_null, keep, cond_scale, known, kmask, out=None):
+    """the logits of one denoise step with the known pixels in them (dmh_known_blend; the definition:
+    include/dmhomo_hip_known.h): out = known where kmask != 0, else the guided blend of (model_cond, model_null, keep) as
+    sampler_step reads it — model_null and keep may be None.  A select: a NaN logit under a kept element is gone.  kmask: uint8,
+    one per element.  out None: model_cond itself, in place; out must not be model_null, known or kmask.  It reads no DmhStep: the
+    same call serves the eager and the replayed loop, and — model_null None, cond_scale 1, in place on the unnormalised image
+    with the caller's own values — the write-back behind the loop.  The result goes to sampler_step / sampler_step_ms /
+    sampler_threshold + sampler_step_thr as model_cond with model_null = None.  -> out"""
+    B, n = _known_shapes('known_blend', model_cond, model_null, keep, known, kmask)
+    out = model_cond if out is None else out
+    if tuple(out.shape) != tuple(model_cond.shape):
+        raise ValueError(f'known_blend: out {tuple(out.shape)} against model_cond {tuple(model_cond.shape)}')
+    if _aliases(out, model_null) or _aliases(out, known) or _aliases(out, kmask):
+        raise ValueError('known_blend: out aliases model_null, known or kmask (in place means out is model_cond)')
+    cs = float(cond_scale)
+    if not math.isfinite(cs):
+        raise ValueError(f'known_blend: cond_scale = {cs!r} is not finite')
+    call('dmh_known_blend', ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), cs, ptr(known), ptr(kmask, torch.uint8),
+         ptr(out), B, n)
+    return out
+
+
+def known_error_splits(B, n):
+    """workgroups per row of the known-pixel score's first pass (dmh_known_error_splits): a pure function of (B, n)"""
+    s = int(_lib.lib().dmh_known_error_splits(int(B), int(n)))
+    if s < 1:
+        raise ValueError(f'known_error_splits: B = {B} rows of n = {n} elements')
+    return s
+
+
+def known_error_workspace(x):
+    """the fp64 workspace dmh_known_error asks for with logits of x's shape (B, ...): 2 doubles per (row, split)"""
+    B = x.shape[0]
+    return torch.empty((2 * B * known_error_splits(B, x.numel() // B),), device=x.device, dtype=torch.float64)
+
+
+def known_error(model_cond, model_null, keep, cond_scale, known, kmask, ws=None, out=None):
+    """how far logits are from the pixels they were told to keep (dmh_known_error): per row the mean over the kept elements
+    (kmask != 0) of (x - known) ** 2, x the guided blend of (model_cond, model_null, keep) as known_blend reads it; float64, a
+    fixed summation order; 0 for a row with nothing kept.  ws: known_error_workspace(model_cond).  -> (B,) float64"""
+    B, n = _known_shapes('known_error', model_cond, model_null, keep, known, kmask)
+    ws = known_error_workspace(model_cond) if ws is None else ws
+    out = _empty((B,), model_cond, torch.float64) if out is None else out
+    if tuple(out.shape) != (B,) or ws.numel() < 2 * B * known_error_splits(B, n) or _aliases(out, ws):
+        raise ValueError(f'known_error: out {tuple(out.shape)} / ws of {ws.numel()} doubles for {B} rows of {n} (and out is not ws)')
+    call('dmh_known_error', ptr(model_cond), ptr(model_null), ptr(keep, torch.uint8), float(cond_scale), ptr(known),
+         ptr(kmask, torch.uint8), ptr(ws, torch.float64), ptr(out, torch.float64), B, n)
+    return out
+
+
 def affine_rows_keep(x, scale, shift, keep, out=None):
     """affine with a keep bit per row (dmh_affine_rows_keep): out[b] = scale * x[b] + shift where keep[b] != 0, else +0.0 — the
     normalisation of rgb_flow and the drop of ``flow_drop_prob`` in one launch.  keep: (B,) uint8."""

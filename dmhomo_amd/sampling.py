@@ -264,13 +264,34 @@ class ScheduleHost:
         c = (1 - alpha_next - sigma ** 2).clamp(min=0).sqrt()
         return float(alpha_next.sqrt()), float(c), float(sigma)
 
-    def _ddim_steps(self, clip, cond_scale=1.):
+    def _stay_coef(self, host, time, time_next):
+        """(c0, c1, c2) of a "stay" entry time -> time in front of the entry time -> time_next (known_resample): the entry's
+        DDIM step followed by re-noising back to ``time`` is, in distribution, one DDIM update with a = abar[time], a' =
+        abar[time_next] (1 for the entry that returns x_0) and that entry's (sigma, c) (0, 0 for the last):  c0 = sqrt(a), c1 =
+        sqrt(a / a') c, c2 = sqrt((a / a') sigma^2 + 1 - a / a'), so that c1^2 + c2^2 = 1 - a.  float64 from the fp32
+        alphas_cumprod buffer, sigma and c by the formulas of _ddim_coef."""
+        abar = host['alphas_cumprod'].double()
+        a = float(abar[time])
+        if time_next < 0:
+            a1, sigma, c = 1., 0., 0.
+        else:
+            a1 = float(abar[time_next])
+            sigma = float(self.ddim_sampling_eta) * math.sqrt((1. - a / a1) * (1. - a1) / (1. - a))
+            c = math.sqrt(max(1. - a1 - sigma * sigma, 0.))
+        q = a / a1
+        return math.sqrt(a), math.sqrt(q) * c, math.sqrt(q * sigma * sigma + 1. - q)
+
+    def _ddim_steps(self, clip, cond_scale=1., stays=0):
         """the DDIM loop (CFG:683-707, DDP:700-726) as a list of (time, DmhStep, draws noise): every step but the last
         draws noise and moves to time_next; the last (time_next < 0) returns x_start and draws nothing.  The eager loops
-        and the replayed loop's step tables all read this list."""
+        and the replayed loop's step tables all read this list.  stays (known_resample - 1, sample_known only): that many
+        "stay" entries time -> time in front of every entry (_stay_coef), each a DDIM update that draws noise."""
         host = self._host()
         steps = []
         for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
+            for _ in range(stays):
+                steps.append((time, self._step(host, time, ops.MODE_DDIM, clip, self._stay_coef(host, time, time_next),
+                                               cond_scale), 1))
             if time_next < 0:
                 steps.append((time, self._step(host, time, ops.MODE_LAST, clip, cond_scale=cond_scale), 0))
             else:
@@ -326,9 +347,48 @@ class ScheduleHost:
             steps.append((time, self._step(host, time, ops.MODE_MULTISTEP, clip, c, cond_scale), 0))
         return steps
 
-    def _sampler_steps(self, clip, cond_scale=1.):
-        """the step list of the selected sampler"""
-        return self._dpmpp_steps(clip, cond_scale) if self._check_sampler() == 'dpmpp_2m' else self._ddim_steps(clip, cond_scale)
+    def _sampler_steps(self, clip, cond_scale=1., stays=0):
+        """the step list of the selected sampler (stays: _ddim_steps; the multistep solver has none: _check_known)"""
+        if self._check_sampler() == 'dpmpp_2m':
+            if stays:
+                raise ValueError(f"{stays} stay entries with sampler = 'dpmpp_2m': its history has no meaning across a stay")
+            return self._dpmpp_steps(clip, cond_scale)
+        return self._ddim_steps(clip, cond_scale, stays)
+
+    # OPT-IN, through cfg.GaussianDiffusion.sample_known only (sample() knows none of it: every existing result, launch, RNG draw
+    # and graph key stays what it is).  sample_known(known, known_mask, ...) keeps the elements of the image pair that known_mask
+    # marks and generates the rest around them (include/dmhomo_hip_known.h has the definition): at every entry of the time list
+    # the logits the update would read — behind flow_guidance / pag_scale, apg_eta or photo_guidance where those are on — are
+    # replaced by K = 2 * known - 1 on the kept elements (dmh_known_blend, a select) and go through the existing step and threshold
+    # kernels as a conditional output without a null pass; behind the last entry's unnormalise the kept elements are overwritten
+    # with ``known`` itself, so they — and their bytes in a record — come back bit for bit.  known_resample = r >= 1: RePaint's
+    # harmonisation with jump length 1 (Lugmayr et al. 2022): r - 1 "stay" entries t -> t in front of every entry (_stay_coef), r
+    # times the network passes; at r = 1 the generator is consumed exactly as by sample().  score_known: the call leaves
+    # last_known_error (B,) float64, the mean squared difference over a sample's kept elements between the last entry's own
+    # logits and K (dmh_known_error): how far the model's final prediction is from the pixels it was told to keep.  Refused with
+    # another objective than pred_x0 (the overwrite acts on the predicted pair), with clip_mode = 'dynamic' (the threshold's
+    # division would move kept pixels), with guidance_rescale > 0 (it rescales a blend the overwrite replaces) and, at r > 1, with
+    # sampler = 'dpmpp_2m' (its history has no meaning across a stay).  What it does to samples of trained weights has not been
+    # measured.  The unconditional class does not have it.
+    known_resample = 1
+    score_known = False
+
+    def _check_known(self):
+        """-> stays = known_resample - 1 of a sample_known call, after the refusals"""
+        r = self.known_resample
+        if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+            raise ValueError(f'known_resample = {r!r}: an int >= 1')
+        if self.objective != 'pred_x0':
+            raise ValueError(f'sample_known with objective = {self.objective!r}: the overwrite acts on the predicted image pair, '
+                             f'which the network returns under pred_x0 only')
+        if self._check_clip_mode() == 'dynamic':
+            raise ValueError("sample_known with clip_mode = 'dynamic': the threshold's division would move the kept pixels")
+        if self._check_guidance_rescale() > 0.:
+            raise ValueError(f'sample_known together with guidance_rescale = {self.guidance_rescale!r}: the rescale works on the '
+                             f'blend that the overwrite replaces')
+        if r > 1 and self._check_sampler() == 'dpmpp_2m':
+            raise ValueError(f"known_resample = {r!r} with sampler = 'dpmpp_2m': its history has no meaning across a stay")
+        return r - 1
 
     # OPT-IN, 'static' by default (every existing result stays what it is).  'dynamic': where a step of the conditional
     # class's sample() clamps x_start to [-1, 1], it instead takes, per sample, s = the ``dynamic_threshold_percentile``-th

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3] [--keep source --known_resample 2]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -37,6 +37,13 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     structurally degraded prediction; it needs no label and no retraining, so it works on any existing checkpoint; 0 is the
     unguided sampler at the cost of the extra pass, the default, off, is the reference's sampler.  Not together with
     --flow_guidance or --guidance_interval; the passes then run as one batched launch sequence (cfg_mode = 'batched');
+  * --keep source|target keeps that image of every batch's own pair (channels 0-5 of a dataset batch) and generates only the
+    other one around it (GaussianDiffusion.sample_known; an addition): the kept image's bytes in the record are the batch's;
+    --known_resample R >= 1 runs every entry of the time list R times (RePaint's harmonisation with jump length 1, Lugmayr et
+    al. 2022; R times the UNet passes); each batch's mean known-pixel score — how far the model's final prediction is from the
+    pixels it was told to keep — is printed.  With SyntheticConditions, whose image channels are zeros, the switch pins a black
+    image: it is meant for --conditions / a dataset folder.  Not together with --clip_mode dynamic or --guidance_rescale, and
+    --known_resample > 1 not with --sampler dpmpp_2m; the default, off, is the reference's sampler;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -109,6 +116,12 @@ parser.add_argument('--flow_guidance', type=float, default=None,
 parser.add_argument('--pag_scale', type=float, default=None,
                     help='scale >= 0 of perturbed-attention guidance: every step also runs a pass whose bottleneck self-attention '
                          'map is the identity (not in the reference; GaussianDiffusion.pag_scale); default: off')
+parser.add_argument('--keep', choices=('source', 'target'), default=None,
+                    help="keep this image of every batch's own pair and generate the other one around it (not in the reference; "
+                         "GaussianDiffusion.sample_known, Trainer.keep); default: off")
+parser.add_argument('--known_resample', type=int, default=1,
+                    help='with --keep: run every entry of the time list this many times (RePaint, jump length 1; '
+                         'ScheduleHost.known_resample); 1: none')
 args = parser.parse_args()
 
 num_classes = 1
@@ -149,6 +162,8 @@ def main():
     if args.pag_scale is not None:
         sampler.model.cfg_mode = 'batched'                 # the perturbed pass rides in the one batched launch sequence
     trainer.score_photometric = args.photo_guidance is not None
+    trainer.keep, sampler.known_resample = args.keep, args.known_resample
+    trainer.score_known = args.keep is not None
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
@@ -165,6 +180,8 @@ def main():
         print(f'length of trainList {len(train_list)}')
         if trainer.score_photometric:
             print(f'rank {rank}: mean photometric error of batch {b}: {float(trainer.last_photometric_error.mean()):.6e}')
+        if trainer.score_known:
+            print(f'rank {rank}: mean known-pixel error of batch {b}: {float(trainer.last_known_error.mean()):.6e}')
         if len(train_list) % 2 == 0:
             np.save(f'{out_dir}idx_{args.i}_rank_{rank}_part_{part}_dm_cahomo_{len(train_list) * args.bs / 1000}k.npy',
                     np.array(train_list, dtype=object), allow_pickle=True)
