@@ -14,7 +14,7 @@ from . import _params as P
 from . import ops
 from .engine import UnetEngine
 from .sampling import DeviceRng, ModelPrediction, ScheduleHost, default, exists, extract  # noqa: F401
-from .schedule import make_buffers, ddim_pairs, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
+from .schedule import make_buffers, ddim_pairs, start_entry, linear_beta_schedule, cosine_beta_schedule  # noqa: F401
 
 
 class Unet(nn.Module):
@@ -428,6 +428,37 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 known['err'] = err
         return ops.known_blend(cond, null, computed, cs, kst['K'], known['mask'], out=kst['logits']), more
 
+    # ---- start from a pair (sample_from; include/dmhomo_hip_start.h has the definition, schedule.start_entry the strength -> entry
+    # map).  OPT-IN, through sample_from only: sample() and sample_known() know none of it, every existing result, launch, RNG draw
+    # and graph key stays what it is.  The loops take ``start``; their first image is then ca * (2 * init - 1) + cb * eps in ONE launch
+    # (dmh_start_mix: eps is the draw sample() uses as its initial image) and they walk the time list from entry k0 on.  Everything
+    # per step — every guidance switch, both clip modes, both samplers, known pixels — acts per entry and knows nothing of where the
+    # list starts.  What it does to samples of trained weights has not been measured.  The unconditional class does not have it.
+    last_start = None                                        # (k0, t*) of the last sample_from call
+
+    def _start_inputs(self, init, strength, shape):
+        """the checks of a sample_from call, once per call -> {'init': (B, 6, H, W) fp32 in [0, 1], 'k0': the first entry that
+        runs, 't': its time, 'ca', 'cb': the fp32 buffer values q_sample reads at t}, what the loops take as ``start``"""
+        k0 = start_entry(self.sampling_timesteps, strength)
+        device = self.betas.device
+        if not torch.is_tensor(init) or tuple(init.shape) != tuple(shape):
+            raise ValueError(f'sample_from: init {tuple(init.shape) if torch.is_tensor(init) else type(init).__name__} '
+                             f'against the image pair {tuple(shape)}')
+        init = init.to(device=device, dtype=torch.float32).contiguous()
+        if not bool(((init >= 0.) & (init <= 1.)).all()):    # (a NaN fails both comparisons)
+            raise ValueError('sample_from: init has values outside [0, 1], the range of the sampler\'s output and of the '
+                             'dataset\'s image channels')
+        host = self._host()
+        t = ddim_pairs(self.num_timesteps, self.sampling_timesteps)[k0][0]
+        return {'init': init, 'k0': k0, 't': t, 'ca': float(host['sqrt_alphas_cumprod'][t]),
+                'cb': float(host['sqrt_one_minus_alphas_cumprod'][t])}
+
+    def _first_image(self, shape, device, start):
+        """the image a loop begins with: the generator's first draw of the call, or — ``start`` — the pair noised to its time"""
+        if start is None:
+            return self.rng.randn(shape, device).contiguous()
+        return self.rng.start_mix(start['init'], start['ca'], start['cb'])
+
     # OPT-IN, None by default (every existing result, launch, RNG draw and graph key stays what it is).  flow_guidance = s_f, a
     # finite number >= 0: classifier-free guidance on the homography condition in sample() — the label of this data set sits in
     # rgb_flow * mask (the class is always 0, DDP:1136), which reaches the network through three stem channels only.  With the switch
@@ -541,15 +572,17 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         """CFG:669-711."""
         return self._ddim_sample(classes, rgb_flow, flow, mask, shape, cond_scale, clip_denoised)
 
-    def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None):
+    def _ddim_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None,
+                     start=None):
         """ddim_sample; ``trace`` (list) optionally receives per-step x_start / img for parity tests (and, with clip_mode =
         'dynamic', the step's thresholds 'thr'; with guidance_rescale, its factors 'gfac' at the guided entries; 'guided': whether
         the entry ran with the null pass, False only under guidance_interval; with apg_eta, the step's (A, Cc) per row, 'apg' (B, 2);
         with photo_guidance, the photometric energy of the blend before the correction, 'photo' (B,) float64; with ``known``, the
         score of the entry's logits 'known_err' (B,) float64, and 'stay': True on the stay entries of known_resample).
-        known: what _known_inputs returns (sample_known), or None: the loop as it was."""
+        known: what _known_inputs returns (sample_known), or None: the loop as it was.  start: what _start_inputs returns
+        (sample_from), or None: the loop as it was."""
         batch, device = shape[0], self.betas.device
-        steps = self._ddim_steps(clip_denoised, cond_scale, known['stays'] if known else 0)
+        steps = self._ddim_steps(clip_denoised, cond_scale, known['stays'] if known else 0, start['k0'] if start else 0)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
@@ -560,7 +593,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
         if pg is not None:
             tag = {'pag': True}
-        img = self.rng.randn(shape, device).contiguous()
+        img = self._first_image(shape, device, start)
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
         pst = self._photo_state(shape, flow, mask, device) if photo else None
@@ -632,12 +665,14 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                                            keep=computed)
         return img, x_start, {'gfac': gfac, **({} if thr is None else {'thr': thr})}
 
-    def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None):
+    def _dpmpp_sample(self, classes, rgb_flow, flow, mask, shape, cond_scale=3., clip_denoised=True, trace=None, known=None,
+                      start=None):
         """the loop of _ddim_sample with the multistep solver's update (ScheduleHost._dpmpp_steps; not in the reference): the
         network call — its class-dropout draw included — is the same, the update draws nothing and carries the previous step's
-        x_start in ``hist``.  ``trace`` and ``known`` as _ddim_sample (no stay entries: _check_known)."""
+        x_start in ``hist``.  ``trace``, ``known`` and ``start`` as _ddim_sample (no stay entries: _check_known; the solver's
+        coefficients are those of the list that begins at start['k0'])."""
         batch, device = shape[0], self.betas.device
-        steps = self._dpmpp_steps(clip_denoised, cond_scale)
+        steps = self._dpmpp_steps(clip_denoised, cond_scale, start['k0'] if start else 0)
         guided = self._guided_entries([t for t, _, _ in steps], cond_scale)
         rank = self._dynamic_rank(shape, clip_denoised)
         phi = self._rescale_phi(cond_scale)
@@ -648,7 +683,7 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         pg = self._check_pag()                               # None: off, else s.  (It refuses flow_guidance, an interval, 'streams'.)
         if pg is not None:
             tag = {'pag': True}
-        img = self.rng.randn(shape, device).contiguous()
+        img = self._first_image(shape, device, start)
         hist = torch.empty_like(img)                         # (entry 0 has c2 == 0: never read before it is written)
         ws = ops.guidance_workspace(img) if phi else None
         ast = self._apg_state(img, apg) if apg else None
@@ -742,13 +777,43 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             self.last_known_error = kn['err']
         return out
 
-    def _graph_tables(self, cond_scale, clip=True, stays=0):
+    @torch.no_grad()
+    def sample_from(self, init, strength, classes, rgb_flow, flow, mask, cond_scale=3., known=None, known_mask=None):
+        """sample() started from a given pair (SDEdit, Meng et al. 2022 — diffusers' image-to-image ``strength``; not in the
+        reference; include/dmhomo_hip_start.h has the definition): init (B, 6, H, W) fp32 in [0, 1] is noised to the time of entry
+        k0 = schedule.start_entry(sampling_timesteps, strength) of the time list with the generator's first draw, and the loop runs
+        from that entry on: strength * S network entries instead of S.  strength in (0, 1]; 1 runs every entry from q(x_{T-1} |
+        init) (pure noise is sample()).  With ``known`` and ``known_mask`` the loop is sample_known's, started from the mixed
+        image: the kept elements come back bit for bit, the others start from init.  -> (img, mask, flow) like sample; the call
+        leaves last_start = (k0, t*)."""
+        batch_size, image_size, channels = classes.shape[0], self.image_size, self.channels
+        shape = (batch_size, channels, image_size, image_size)
+        if (known is None) != (known_mask is None):
+            raise ValueError('sample_from: known and known_mask go together (both, or neither)')
+        st = self._start_inputs(init, strength, shape)
+        kn = None if known is None else self._known_inputs(known, known_mask, shape)
+        solver = self._check_sampler() == 'dpmpp_2m'
+        if not self.is_ddim_sampling and not solver:
+            return self.p_sample_loop(classes, rgb_flow, flow, mask, shape, cond_scale)    # TypeError, as sample()
+        self.last_start = (st['k0'], st['t'])
+        if self.hip_graph and type(self.rng) is DeviceRng and self.sampling_timesteps >= 1:
+            out = self._sample_graphed(classes, rgb_flow, flow, mask, shape, cond_scale, known=kn, start=st)
+        else:
+            rgb_flow = ops.affine(rgb_flow.to(torch.float32), 2., -1.)      # normalize_to_neg_one_to_one, CFG:716
+            loop = self._dpmpp_sample if solver else self._ddim_sample
+            out = loop(classes, rgb_flow, flow, mask, shape, cond_scale, known=kn, start=st)
+        if kn is not None and kn['score']:
+            self.last_known_error = kn['err']
+        return out
+
+    def _graph_tables(self, cond_scale, clip=True, stays=0, first=0):
         """host side of the replayed loop: (steps, times, draws), entry k = the DmhStep, timestep and 'draws noise' flag
-        _ddim_sample (or, with sampler = 'dpmpp_2m', _dpmpp_sample) passes at its k-th step (stays: sample_known's stay entries)."""
-        times, steps, draws = map(list, zip(*self._sampler_steps(clip, cond_scale, stays)))
+        _ddim_sample (or, with sampler = 'dpmpp_2m', _dpmpp_sample) passes at its k-th step (stays: sample_known's stay entries;
+        first: the time pairs from ``first`` on, sample_from under 'dpmpp_2m')."""
+        times, steps, draws = map(list, zip(*self._sampler_steps(clip, cond_scale, stays, first)))
         return steps, times, draws
 
-    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale, known=None):
+    def _sample_graphed(self, classes, rgb_flow, flow, mask, shape, cond_scale, known=None, start=None):
         """sample() with hip_graph (ScheduleHost._replay_captured): one step of CFG:683-707 captured and replayed S times.
         With sampler = 'dpmpp_2m' the step is the network, dmh_sampler_step_ms_dev on a static history buffer and the seek:
         no randn launch is left in it.  With clip_mode = 'dynamic' the update is two calls, dmh_sampler_threshold_dev and
@@ -769,7 +834,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         between those and the update on static buffers (K, known, the expanded mask, the overwritten logits; with score_known the
         fp64 workspace and the result, written by dmh_known_error in the last step only): fill copies this call's known and mask,
         whose values are not part of the key — only that the feature is on, known_resample and score_known are —, the stay entries
-        are entries of the step table, and last() ends with the unnormalise and the write-back."""
+        are entries of the step table, and last() ends with the unnormalise and the write-back.  With ``start`` (sample_from) fill writes
+        st['img'] with dmh_start_mix instead of the first draw and the replay begins at a later entry.  Under 'ddim' the table is the full
+        table and nothing about the start is in the key: the call replays sample()'s (or sample_known's) capture from entry k0 *
+        (stays + 1) on, and changing strength or init never captures again.  Under 'dpmpp_2m' the coefficients depend on k0: the table is
+        built over pairs[k0:] and the key gains ('first', k0), only when k0 > 0."""
         m, eng, device = self.model, self.model._engine, classes.device
         clip = True                                          # ddim_sample's clip_denoised default, as sample() calls it
         solver = self._check_sampler() == 'dpmpp_2m'
@@ -799,6 +868,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
         stays = known['stays'] if known else 0
         if known:                                            # (the table's length and the score's launches: baked in; the pixels not)
             key = key + (('known', stays + 1, known['score']),)
+        k0 = start['k0'] if start else 0
+        tfirst = k0 if solver else 0                         # the pair the capture's table begins at
+        if tfirst:                                           # (the solver's coefficients over pairs[k0:]: baked into the table)
+            key = key + (('first', k0),)
 
         def buffers(st, times, draws):
             ins = st['ins'] = [classes.clone(), rgb_flow.to(torch.float32).clone(), mask.clone()]
@@ -901,7 +974,10 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
             for dst, src in zip(st['ins'], (classes, rgb_flow, mask)):
                 dst.copy_(src)
             ops.affine(st['ins'][1], 2., -1., out=st['rf'])  # normalize_to_neg_one_to_one, CFG:716
-            st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
+            if start is None:
+                st['img'].copy_(self.rng.randn(shape, device))   # CFG:679
+            else:                                            # the pair noised to the time of entry k0, with that same draw
+                self.rng.start_mix(start['init'], start['ca'], start['cb'], out=st['img'])
             if apg and st['apg_run'] is not None:
                 st['apg_run'].zero_()                        # the running average starts every loop at zero
             if photo:                                        # this call's flow and mask, and the preconditioner they give
@@ -913,9 +989,11 @@ class GaussianDiffusion(nn.Module, ScheduleHost):
                 ops.affine(st['known_01'], 2., -1., out=st['known_K'])
                 st['known_mask'].copy_(known['mask'])
             if gated:
-                flags = self._guided_entries(self._graph_tables(cond_scale, clip, stays)[1], cond_scale)
+                flags = self._guided_entries(self._graph_tables(cond_scale, clip, stays, tfirst)[1], cond_scale)
                 st['guided'].copy_(torch.tensor(flags, dtype=torch.uint8))
-        img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip, stays), buffers, fill)
+        first = (k0 - tfirst) * (stays + 1)                  # the entry of the capture's table the replay begins at
+        img = self._replay_captured(shape, device, key, lambda: self._graph_tables(cond_scale, clip, stays, tfirst), buffers, fill,
+                                    **({'first': first} if first else {}))
         if known and known['score']:
             known['err'] = self.__dict__['_graph_state']['known_err'].clone()
         return img, mask, flow

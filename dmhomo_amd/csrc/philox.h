@@ -44,4 +44,28 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t draw, uint64_t s
   box_muller(r.z, r.w, v[2], v[3]);
 }
 
+// The end of a launch that consumes one draw of the keyed generator (state: seed, draw index, tickets, reserved).  Every
+// workgroup has read the draw index before it takes a ticket; the last one to arrive advances it and puts the ticket counter
+// back, both visible to the next launch on the stream.  All threads of the workgroup call it.
+__device__ __forceinline__ void advance_draw(unsigned long long* state, unsigned long long draw) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long total = (unsigned long long)gridDim.x * gridDim.y;
+    const unsigned long long t = atomicAdd(&state[2], 1ull);
+    if (t == total - 1) {
+      state[2] = 0;
+      state[1] = draw + 1;
+    }
+  }
+}
+
+// workgroups per sample of such a launch over B rows of nq counter quads, 256 threads each.  Every workgroup ends with a
+// returning atomic on ONE word (the arrival ticket): at 2400 workgroups those tickets were most of the launch (33 us for 2.4 M
+// normals).  About two workgroups per CU in total, each looping over its share
+static inline unsigned draw_grid_x(int B, int64_t nq) {
+  int64_t gx = cdiv64(nq, 256);
+  const int64_t cap = B >= 512 ? 1 : 512 / B;
+  return (unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx));
+}
+
 }  // namespace dmh_philox

@@ -46,17 +46,7 @@ __global__ __launch_bounds__(256) void rng_indexed_kernel(float* __restrict__ ou
       for (int j = 0; j < 4 && e + j < per; ++j) o[e + j] = v[j];
     }
   }
-  // every workgroup has read the draw index before it takes a ticket; the last one to arrive advances it and puts the
-  // ticket counter back, both visible to the next launch on the stream
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long total = (unsigned long long)gridDim.x * gridDim.y;
-    const unsigned long long t = atomicAdd(&state[2], 1ull);
-    if (t == total - 1) {
-      state[2] = 0;
-      state[1] = draw + 1;
-    }
-  }
+  advance_draw(state, draw);   // (philox.h: the arrival ticket)
 }
 
 // the class-dropout mask of CFG:84-90 in one launch: keep[b] = uniform(seed, sample id, draw, element 0) < prob, as uint8 —
@@ -90,12 +80,8 @@ extern "C" int dmh_rng_indexed(float* out, int B, int64_t per_sample, const int6
   DMH_REQUIRE(B <= 65535, "dmh_rng_indexed: B=%d (limit 65535 rows per launch)", B);
   DMH_REQUIRE(per_sample < ((int64_t)1 << 34), "dmh_rng_indexed: %lld elements per sample (limit 2^34)", (long long)per_sample);
   const int64_t nq = (per_sample + 3) >> 2;
-  // every workgroup ends with a returning atomic on ONE word (the arrival ticket): at 2400 workgroups those tickets were most
-  // of the launch (33 us for 2.4 M normals).  About two workgroups per CU in total, each looping over its share
-  int64_t gx = cdiv64(nq, 256);
-  const int64_t cap = B >= 512 ? 1 : 512 / B;
-  gx = gx < 1 ? 1 : (gx > cap ? cap : gx);
-  hipLaunchKernelGGL(rng_indexed_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, out, per_sample,
+  const unsigned gx = draw_grid_x(B, nq);   // (philox.h: few workgroups, each looping over its share)
+  hipLaunchKernelGGL(rng_indexed_kernel, dim3(gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, out, per_sample,
                      sample_ids, (unsigned long long*)state, kind);
   DMH_CHECK_LAUNCH("dmh_rng_indexed");
   return DMH_OK;

@@ -618,7 +618,12 @@ class Trainer(object):
     (channels 0-5 of every dataset batch are img1 | img2) and generates only the other one around it, through
     ``sample_known`` of the conditional sampler; the kept image's bytes in the record are the batch's.  The record format is
     unchanged.  ``score_known`` (off by default): with ``keep``, the call also leaves the sampler's ``last_known_error``, (B,)
-    float64, in ``last_known_error``."""
+    float64, in ``last_known_error``.
+
+    ``strength`` (class attribute, None by default): a number in (0, 1] — ``sample`` starts from the batch's own pair (channels
+    0-5) noised to an intermediate time and denoises it under the batch's condition, through ``sample_from`` of the conditional
+    sampler: strength * sampling_timesteps network entries instead of all.  Together with ``keep`` the kept image stays the
+    batch's and the other one starts from the batch's instead of from pure noise.  The record format is unchanged."""
 
     preview = False
     score_photometric = False
@@ -626,6 +631,7 @@ class Trainer(object):
     keep = None
     score_known = False
     last_known_error = None
+    strength = None
 
     def __init__(self, diffusion_model, folder, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_horizontal_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10,
@@ -781,6 +787,10 @@ class Trainer(object):
         rgb_flows = data[0][:, -5:-2].to(dev)
         flows = data[0][:, -2:].to(dev).contiguous()
         mask = data[0][:, -6:-5].to(dev)
+        if self.strength is not None and not hasattr(self.ema.ema_model, 'sample_from'):
+            sampler = self.ema.ema_model
+            raise ValueError(f'Trainer.strength = {self.strength!r}: {type(sampler).__module__}.{type(sampler).__name__} has no '
+                             f'sample_from (the conditional sampler has)')
         if self.keep is not None:
             if self.keep not in ('source', 'target'):
                 raise ValueError(f"Trainer.keep = {self.keep!r}: None, 'source' or 'target'")
@@ -792,12 +802,21 @@ class Trainer(object):
             sampler.score_known = bool(self.score_known) or was
             try:
                 with torch.no_grad():
-                    all_images = sampler.sample_known(data[0][:, :6].to(dev), self.keep, classes=data[1].to(dev),
-                                                      rgb_flow=rgb_flows, flow=flows, mask=mask)
+                    if self.strength is None:
+                        all_images = sampler.sample_known(data[0][:, :6].to(dev), self.keep, classes=data[1].to(dev),
+                                                          rgb_flow=rgb_flows, flow=flows, mask=mask)
+                    else:                                    # the kept image stays, the other one starts from the batch's own
+                        pair = data[0][:, :6].to(dev)
+                        all_images = sampler.sample_from(pair, self.strength, classes=data[1].to(dev), rgb_flow=rgb_flows,
+                                                         flow=flows, mask=mask, known=pair, known_mask=self.keep)
             finally:
                 sampler.score_known = was
             if self.score_known:
                 self.last_known_error = sampler.last_known_error
+        elif self.strength is not None:
+            with torch.no_grad():
+                all_images = self.ema.ema_model.sample_from(data[0][:, :6].to(dev), self.strength, classes=data[1].to(dev),
+                                                            rgb_flow=rgb_flows, flow=flows, mask=mask)
         else:
             with torch.no_grad():
                 all_images = self.ema.ema_model.sample(classes=data[1].to(dev), rgb_flow=rgb_flows, flow=flows, mask=mask)

@@ -1039,6 +1039,23 @@ def rng_indexed(shape, sample_ids, state, kind=0):
     return out
 
 
+def start_mix(init01, ca, cb, *, noise=None, sample_ids=None, state=None, out=None):
+    """the start image of sample_from in one launch (dmh_start_mix; the definition: include/dmhomo_hip_start.h): out = ca * (2 *
+    init01 - 1) + cb * eps, every operation rounded separately — q_sample(affine(init01, 2, -1), eps) bit for bit.  eps: ``noise``,
+    or the next draw of the keyed generator (``sample_ids``, ``state``; the launch advances the draw index as rng_indexed does and
+    the noise never exists in memory); the entry refuses both or neither.  out may be ``noise`` itself.  -> out"""
+    B = int(init01.shape[0])
+    out = torch.empty_like(init01) if out is None else out
+    if tuple(out.shape) != tuple(init01.shape) or (noise is not None and tuple(noise.shape) != tuple(init01.shape)):
+        raise ValueError(f'start_mix: out {tuple(out.shape)} / noise {None if noise is None else tuple(noise.shape)} against '
+                         f'init01 {tuple(init01.shape)}')
+    if (sample_ids is not None and tuple(sample_ids.shape) != (B,)) or (state is not None and tuple(state.shape) != (4,)):
+        raise ValueError(f'start_mix: sample_ids of {B} int64 (one per row) and state of 4 int64 expected')
+    call('dmh_start_mix', ptr(init01), ptr(noise), ptr(sample_ids, torch.int64), ptr(state, torch.int64), float(ca), float(cb),
+         ptr(out), B, init01.numel() // B)
+    return out
+
+
 def rng_keep_mask(sample_ids, state, prob):
     """(B,) uint8: uniform draw of the indexed generator < prob (the class-dropout mask of CFG:84-90), one launch."""
     B = sample_ids.shape[0]

@@ -104,6 +104,15 @@ class DeviceRng:
             return ops.rng_indexed((n,), self.ids_for(n), self.state, 1)
         return torch.zeros((n,), device=device).float().uniform_(0, 1)
 
+    def start_mix(self, init01, ca, cb, out=None):
+        """ca * (2 * init01 - 1) + cb * eps with eps the next randn(init01.shape) of this generator, in one launch of
+        dmh_start_mix: keyed, the kernel draws eps itself and advances the draw index; else torch's generator draws it and the
+        kernel reads it.  -> out"""
+        if self.keyed:
+            return ops.start_mix(init01, ca, cb, sample_ids=self.ids_for(init01.shape[0]), state=self.state, out=out)
+        noise = self.randn(init01.shape, init01.device)
+        return ops.start_mix(init01, ca, cb, noise=noise, out=noise if out is None else out)
+
 
 class ScheduleHost:
     """what the two GaussianDiffusion classes share.  The constructor body, q_sample, the loss target.  Host mirrors of the
@@ -281,14 +290,15 @@ class ScheduleHost:
         q = a / a1
         return math.sqrt(a), math.sqrt(q) * c, math.sqrt(q * sigma * sigma + 1. - q)
 
-    def _ddim_steps(self, clip, cond_scale=1., stays=0):
+    def _ddim_steps(self, clip, cond_scale=1., stays=0, first=0):
         """the DDIM loop (CFG:683-707, DDP:700-726) as a list of (time, DmhStep, draws noise): every step but the last
         draws noise and moves to time_next; the last (time_next < 0) returns x_start and draws nothing.  The eager loops
         and the replayed loop's step tables all read this list.  stays (known_resample - 1, sample_known only): that many
-        "stay" entries time -> time in front of every entry (_stay_coef), each a DDIM update that draws noise."""
+        "stay" entries time -> time in front of every entry (_stay_coef), each a DDIM update that draws noise.  first (sample_from:
+        schedule.start_entry): the list over the time pairs from ``first`` on — the tail of the full list, each pair's stays with it."""
         host = self._host()
         steps = []
-        for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps):
+        for time, time_next in ddim_pairs(self.num_timesteps, self.sampling_timesteps)[first:]:
             for _ in range(stays):
                 steps.append((time, self._step(host, time, ops.MODE_DDIM, clip, self._stay_coef(host, time, time_next),
                                                cond_scale), 1))
@@ -312,19 +322,21 @@ class ScheduleHost:
             raise ValueError(f'unknown sampler {self.sampler!r}: one of {self.SAMPLERS}')
         return self.sampler
 
-    def _dpmpp_steps(self, clip, cond_scale=1.):
+    def _dpmpp_steps(self, clip, cond_scale=1., first=0):
         """the DPM-Solver++ 2M loop as a list of (time, DmhStep, 0), over the time pairs of _ddim_steps.  With a_k =
         sqrt(abar[t_k]), s_k = sqrt(1 - abar[t_k]), lam_k = ln(a_k / s_k), h_k = lam_{k+1} - lam_k and e_k = -expm1(-h_k), entry
         k moves to t_{k+1} by  img' = c1 * img + c0 * x0_k + c2 * x0_{k-1}  (x0: the clamped data prediction, as DDIM's):
         c1 = s_{k+1} / s_k; first order (entry 0, and the last entry that updates: 'lower order final') c0 = a_{k+1} e_k,
         c2 = 0; second order, r = h_{k-1} / h_k: c0 = a_{k+1} e_k (1 + 1/(2r)), c2 = -a_{k+1} e_k / (2r).  float64 from the
-        fp32 alphas_cumprod buffer.  The entry with time_next < 0 returns x0 (MODE_LAST)."""
+        fp32 alphas_cumprod buffer.  The entry with time_next < 0 returns x0 (MODE_LAST).  first (sample_from:
+        schedule.start_entry): the solver over the time pairs from ``first`` on — its entry 0, first order, is pair ``first``."""
         host = self._host()
         abar = host['alphas_cumprod'].double()
         pairs = ddim_pairs(self.num_timesteps, self.sampling_timesteps)
         if any(tn >= t for t, tn in pairs):
             raise ValueError(f'dpmpp_2m: the sampling times {[t for t, _ in pairs]} are not strictly decreasing '
                              f'(sampling_timesteps = {self.sampling_timesteps} of {self.num_timesteps}): a step of width 0')
+        pairs = pairs[first:]
 
         def a_s_lam(t):
             a, sg = math.sqrt(float(abar[t])), math.sqrt(1. - float(abar[t]))
@@ -347,13 +359,14 @@ class ScheduleHost:
             steps.append((time, self._step(host, time, ops.MODE_MULTISTEP, clip, c, cond_scale), 0))
         return steps
 
-    def _sampler_steps(self, clip, cond_scale=1., stays=0):
-        """the step list of the selected sampler (stays: _ddim_steps; the multistep solver has none: _check_known)"""
+    def _sampler_steps(self, clip, cond_scale=1., stays=0, first=0):
+        """the step list of the selected sampler (stays: _ddim_steps; the multistep solver has none: _check_known; first: the
+        time pairs from ``first`` on)"""
         if self._check_sampler() == 'dpmpp_2m':
             if stays:
                 raise ValueError(f"{stays} stay entries with sampler = 'dpmpp_2m': its history has no meaning across a stay")
-            return self._dpmpp_steps(clip, cond_scale)
-        return self._ddim_steps(clip, cond_scale, stays)
+            return self._dpmpp_steps(clip, cond_scale, first)
+        return self._ddim_steps(clip, cond_scale, stays, first)
 
     # OPT-IN, through cfg.GaussianDiffusion.sample_known only (sample() knows none of it: every existing result, launch, RNG draw
     # and graph key stays what it is).  sample_known(known, known_mask, ...) keeps the elements of the image pair that known_mask
@@ -528,13 +541,14 @@ class ScheduleHost:
     graph_cache_size = 4
     graph_captures = 0                   # captures made by this object so far (tests count them)
 
-    def _replay_captured(self, shape, device, key, tables, buffers, fill):
+    def _replay_captured(self, shape, device, key, tables, buffers, fill, first=0):
         """Run the sampling loop through the cache of captured steps (above) -> the last step's output (a copy).
         key: what the class bakes into its captures (weights, schedule and device are added here).  tables() -> (steps,
         times, draws), the loop's entries in order (built on a miss only).  buffers(st, times, draws): puts the class's
         static buffers into the new entry ``st`` (which already holds the step table, 'img' and 'tcond') and returns its
         step bodies (mid, last): mid one step in place on st['img'], last the last step, returning the output.
-        fill(st): writes this call's static inputs (and the first noise draw into st['img']) in front of the replay."""
+        fill(st): writes this call's static inputs (and the first noise draw into st['img']) in front of the replay.
+        first: the entry of the table the replay starts at (sample_from under 'ddim': the capture and its table are sample()'s)."""
         self.model._engine.ensure_prepared()
         self._host()                                         # (host mirrors cached before any capture)
         live = (self.model._engine._sig, self.__dict__['_host_cache'][0], str(device))
@@ -584,8 +598,11 @@ class ScheduleHost:
                 cache.popitem(last=False)                    # least recently used: its graphs, pool and buffers go with it
         self.__dict__['_graph_state'] = st                   # (the entry this call replays)
         fill(st)
-        ops.sampler_seek(st['cursor'], 0, st['table'], st['times'], st['cur'], st['tcond'])
-        for _ in range(st['nsteps'] - 1):
+        first = int(first)
+        if not 0 <= first < st['nsteps']:
+            raise ValueError(f'_replay_captured: first = {first} of {st["nsteps"]} entries')
+        ops.sampler_seek(st['cursor'], first, st['table'], st['times'], st['cur'], st['tcond'])
+        for _ in range(st['nsteps'] - 1 - first):
             st['graph'].replay()
         st['graph_last'].replay()
         return st['out'].clone()

@@ -57,3 +57,20 @@ def ddim_pairs(num_timesteps, sampling_timesteps):
     ts = torch.linspace(-1, num_timesteps - 1, steps=sampling_timesteps + 1).int().tolist()
     ts.reverse()
     return list(zip(ts[:-1], ts[1:]))
+
+
+def start_entry(sampling_timesteps, strength):
+    """the entry of the time list a loop started from a given pair begins at (sample_from; include/dmhomo_hip_start.h): with S =
+    sampling_timesteps, n = min(S, floor(S * strength + 1e-9)) entries run and k0 = S - n is the first of them; its time is
+    ddim_pairs(T, S)[k0][0].  strength: a finite number in (0, 1]; a strength below 1 / S would run no entry and is refused.
+    (1e-9: S * strength for a strength meant as k / S must not land below k, as 22 * (15 / 22) = 14.999999999999998 does.)"""
+    S = int(sampling_timesteps)
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not (0. < float(strength) <= 1.):
+        raise ValueError(f'strength = {strength!r}: a finite number in (0, 1]')       # (a NaN fails both comparisons)
+    if S < 1:
+        raise ValueError(f'sampling_timesteps = {sampling_timesteps!r}: at least one entry')
+    n = min(S, int(math.floor(S * float(strength) + 1e-9)))
+    if n == 0:
+        raise ValueError(f'strength = {strength!r} runs none of the {S} entries of the time list: the smallest strength that '
+                         f'runs one is 1 / {S} = {1. / S!r}')
+    return S - n

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3] [--keep source --known_resample 2]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3] [--keep source --known_resample 2] [--strength 0.5]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -44,6 +44,13 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     pixels it was told to keep — is printed.  With SyntheticConditions, whose image channels are zeros, the switch pins a black
     image: it is meant for --conditions / a dataset folder.  Not together with --clip_mode dynamic or --guidance_rescale, and
     --known_resample > 1 not with --sampler dpmpp_2m; the default, off, is the reference's sampler;
+  * --strength F in (0, 1] starts every batch from its own pair (channels 0-5 of a dataset batch) noised to an intermediate time
+    instead of from pure noise, and runs only the last floor(s_step * F) entries of the time list (GaussianDiffusion.sample_from —
+    SDEdit, Meng et al. 2022; an addition): the real scene, re-labelled under the batch's homography condition, at F times the
+    UNet passes; 1 runs every entry.  Together with --keep the kept image stays the batch's and the other one starts from the
+    batch's.  With SyntheticConditions, whose image channels are zeros, the start is a noised black pair: the flag is meant for
+    --conditions / a dataset folder.  A strength below 1 / s_step runs no entry and is refused; the default, off, is the
+    reference's sampler;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -122,6 +129,10 @@ parser.add_argument('--keep', choices=('source', 'target'), default=None,
 parser.add_argument('--known_resample', type=int, default=1,
                     help='with --keep: run every entry of the time list this many times (RePaint, jump length 1; '
                          'ScheduleHost.known_resample); 1: none')
+parser.add_argument('--strength', type=float, default=None,
+                    help="start every batch from its own pair noised to an intermediate time and run the last floor(s_step * "
+                         "STRENGTH) entries only, STRENGTH in (0, 1] (SDEdit; not in the reference; GaussianDiffusion.sample_from, "
+                         "Trainer.strength); default: off")
 args = parser.parse_args()
 
 num_classes = 1
@@ -164,6 +175,7 @@ def main():
     trainer.score_photometric = args.photo_guidance is not None
     trainer.keep, sampler.known_resample = args.keep, args.known_resample
     trainer.score_known = args.keep is not None
+    trainer.strength = args.strength
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
