@@ -37,10 +37,10 @@ _row('dmh_class_embed', 'test_gpu_fwd_glue.py', ('ops.class_embed',))
 _row('dmh_ss_gather', 'test_gpu_fwd_glue.py', ('ops.ss_gather',))
 _row('dmh_linattn_partial_floats dmh_linattn_context dmh_linattn_merge dmh_linattn_apply dmh_linattn_merge_ms '
      'dmh_linattn_bwd_workspace_floats dmh_linattn_backward dmh_attention', 'test_gpu_attn_core.py')
-_row('dmh_conv_wgrad_workspace_floats', 'test_wgrad_splits_host.py')
-_row('dmh_conv_wgrad', 'test_gpu_wgrad_splits.py test_gpu_backward.py')
-_row('dmh_conv_unshuffle_wgrad_workspace_floats', 'test_ddp_train_host.py')
-_row('dmh_conv_unshuffle_wgrad', 'test_gpu_ddp_train.py')
+_row('dmh_conv_wgrad_workspace_floats', 'test_wgrad_splits_host.py test_grad_conv_host.py')
+_row('dmh_conv_wgrad', 'test_gpu_grad_conv.py test_gpu_wgrad_splits.py test_gpu_backward.py')
+_row('dmh_conv_unshuffle_wgrad_workspace_floats', 'test_ddp_train_host.py test_grad_conv_host.py')
+_row('dmh_conv_unshuffle_wgrad', 'test_gpu_grad_conv.py test_gpu_ddp_train.py')
 _row('dmh_s2d_shift dmh_d2s dmh_sumpool2 dmh_loss_backward dmh_loss_backward_ddp dmh_sumsq dmh_gradnorm_finalize dmh_adam '
      'dmh_adam_multi dmh_sumsq_multi dmh_ema dmh_resize_bilinear_u8 dmh_mask_open_nearest dmh_pixel_grid dmh_norm_grid '
      'dmh_homography_flow_points dmh_homography_flow dmh_flow_to_image', 'test_gpu_aux.py')
