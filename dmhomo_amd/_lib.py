@@ -235,6 +235,13 @@ START_EXTENSIONS = {
     'dmh_start_mix': (c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_float, c_float, c_f32p, c_int, c_i64, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); the entry include/dmhomo_hip_relabel.h declares (ddpm.relabel_batch: a new homography label per
+# sample, drawn on the device), in a table of its own for the same reason
+RELABEL_EXTENSIONS = {
+    'dmh_relabel_batch': (c_int, [c_f32p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, c_float, C.c_void_p, c_int,
+                                  c_f32p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, C.c_void_p]),
+}
+
 DLT_BLOCKS = 64
 
 _lib = None
@@ -252,7 +259,8 @@ def lib():
             raise DmhError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            f'or `make -C dmhomo_amd/csrc` — dmhomo_amd has no CPU / eager fallback')
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSIONS.items()) + list(START_EXTENSIONS.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSIONS.items()) + list(START_EXTENSIONS.items()) + \
+                list(RELABEL_EXTENSIONS.items()):
             fn = getattr(h, name)          # AttributeError if the symbol is missing (a stale library fails here, loudly)
             fn.restype = res
             fn.argtypes = args

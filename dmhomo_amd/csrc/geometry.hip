@@ -1,7 +1,7 @@
 // K7-K9 — condition builder & geometry: homography -> flow -> HSV image, bilinear flow warp,
 // flow -> homography (DLT normal equations).  Mirrors the reference's op order exactly where
 // integers come out (grid-sample corner indices): no FMA contraction in this file.
-#include "geometry_dev.h"   // flow_pixel_to_rgb (G3), flow_warp_taps / flow_warp_sample (G4): shared with preview.hip
+#include "geometry_dev.h"   // homography_flow_pixel (G2), flow_pixel_to_rgb (G3), flow_warp_taps / flow_warp_sample (G4): shared
 
 #pragma clang fp contract(off)
 
@@ -14,13 +14,8 @@ __global__ __launch_bounds__(256) void homography_flow_kernel(const double* __re
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= H * W) return;
   const int yi = p / W, xi = p % W;
-  const double* h = Hm + b * 9;
-  const double x = (double)xi, y = (double)yi;
-  const double qx = h[0] * x + h[1] * y + h[2];
-  const double qy = h[3] * x + h[4] * y + h[5];
-  const double qw = (h[6] * x + h[7] * y + h[8]) + 1e-6;  // DDP:958-959
-  const float u = (float)(qx / qw - x);
-  const float v = (float)(qy / qw - y);
+  float u, v;
+  homography_flow_pixel(Hm + b * 9, xi, yi, u, v);      // geometry_dev.h
   const size_t hw = (size_t)H * W;
   if (flow) {
     flow[((size_t)b * 2 + 0) * hw + p] = u;

@@ -1,10 +1,22 @@
-// Per-pixel device functions of the geometry kernels, shared by geometry.hip (G3 flow_to_image, G4 flow_warp) and preview.hip
-// (the preview sheets fuse both): one definition, so the fused panels are bit for bit what the stand-alone kernels write.
+// Per-pixel device functions of the geometry kernels, shared by geometry.hip (G2 homography flow, G3 flow_to_image, G4 flow_warp),
+// preview.hip (the preview sheets fuse G3 and G4; the homography warp) and relabel.hip (which fuses G2, G3 and the homography
+// warp): one definition, so the fused outputs are bit for bit what the stand-alone kernels write.
 // They mirror the reference's op order where integers come out (grid-sample corner indices): no FMA contraction here.
 #pragma once
 #include "common.h"
 
 #pragma clang fp contract(off)
+
+// G2: get_flow_np DDP:954-967 for one pixel: h . (x, y, 1) in float64 on the integer grid, w' + 1e-6 (DDP:958-959), the
+// subtraction in float64, then the cast.  h: nine doubles, row-major (global memory or LDS)
+__device__ __forceinline__ void homography_flow_pixel(const double* __restrict__ h, int xi, int yi, float& u, float& v) {
+  const double x = (double)xi, y = (double)yi;
+  const double qx = h[0] * x + h[1] * y + h[2];
+  const double qy = h[3] * x + h[4] * y + h[5];
+  const double qw = (h[6] * x + h[7] * y + h[8]) + 1e-6;
+  u = (float)(qx / qw - x);
+  v = (float)(qy / qw - y);
+}
 
 // G3: flow_to_image DDP:1479-1485 + matplotlib.colors.hsv_to_rgb for one pixel
 __device__ __forceinline__ void flow_pixel_to_rgb(float u, float v, float max_flow, float& r, float& g, float& bl) {
@@ -93,4 +105,52 @@ __device__ __forceinline__ void hem_flow_pixel(const double* __restrict__ Hm, in
   const float my = (float)(((Hm[3] * x + Hm[4] * y) + Hm[5]) / (wq + 1e-8));
   u = mx - (float)xi;
   v = my - (float)yi;
+}
+
+// The homography warp (preview.hip: homography_warp_kernel has the contract) in three pieces.
+// 1. the inverse as adjugate times 1 / determinant: inv[k] = adj(m)[k] * (1 / det), zeros for a singular m (cv2.invert)
+__device__ __forceinline__ void homography_inverse(const double* __restrict__ m, double* __restrict__ inv) {
+  const double a0 = m[4] * m[8] - m[5] * m[7], a1 = m[2] * m[7] - m[1] * m[8], a2 = m[1] * m[5] - m[2] * m[4];
+  const double a3 = m[5] * m[6] - m[3] * m[8], a4 = m[0] * m[8] - m[2] * m[6], a5 = m[2] * m[3] - m[0] * m[5];
+  const double a6 = m[3] * m[7] - m[4] * m[6], a7 = m[1] * m[6] - m[0] * m[7], a8 = m[0] * m[4] - m[1] * m[3];
+  const double det = m[0] * a0 + m[1] * a3 + m[2] * a6;
+  const double id = det != 0.0 ? 1.0 / det : 0.0;
+  inv[0] = a0 * id, inv[1] = a1 * id, inv[2] = a2 * id;
+  inv[3] = a3 * id, inv[4] = a4 * id, inv[5] = a5 * id;
+  inv[6] = a6 * id, inv[7] = a7 * id, inv[8] = a8 * id;
+}
+// 2. the source coordinate inv . (x, y, 1) of the destination pixel (xi, yi)  (cv2: w ? 1 / w : 0)
+__device__ __forceinline__ void homography_warp_source(const double* __restrict__ inv, int xi, int yi, double& sx, double& sy) {
+  const double x = (double)xi, y = (double)yi;
+  const double qx = inv[0] * x + inv[1] * y + inv[2];
+  const double qy = inv[3] * x + inv[4] * y + inv[5];
+  const double qw = inv[6] * x + inv[7] * y + inv[8];
+  sx = qw != 0.0 ? qx / qw : 0.0;
+  sy = qw != 0.0 ? qy / qw : 0.0;
+}
+// 3. the exact bilinear sample of one channel plane sc [H][W] at (sx, sy) in float64, rounded once; every tap outside the image
+// reads 0: a coordinate outside (-1, W) x (-1, H) (or NaN) has no tap inside
+struct HomographyWarpTaps {
+  bool any, xl, xr, yt, yb;
+  int x0, y0;      // -1 .. W-1, -1 .. H-1
+  double fx, fy;
+};
+__device__ __forceinline__ HomographyWarpTaps homography_warp_taps(double sx, double sy, int H, int W) {
+  HomographyWarpTaps t;
+  t.any = sx > -1.0 && sx < (double)W && sy > -1.0 && sy < (double)H;
+  const double fx0 = floor(sx), fy0 = floor(sy);
+  t.x0 = t.any ? (int)fx0 : 0;
+  t.y0 = t.any ? (int)fy0 : 0;
+  t.fx = sx - fx0;
+  t.fy = sy - fy0;
+  t.xl = t.x0 >= 0, t.xr = t.x0 + 1 <= W - 1, t.yt = t.y0 >= 0, t.yb = t.y0 + 1 <= H - 1;
+  return t;
+}
+__device__ __forceinline__ float homography_warp_sample(const float* __restrict__ sc, const HomographyWarpTaps& t, int W) {
+  if (!t.any) return 0.f;
+  const double nw = (t.xl && t.yt) ? (double)sc[(size_t)t.y0 * W + t.x0] : 0.0;
+  const double ne = (t.xr && t.yt) ? (double)sc[(size_t)t.y0 * W + t.x0 + 1] : 0.0;
+  const double sw = (t.xl && t.yb) ? (double)sc[(size_t)(t.y0 + 1) * W + t.x0] : 0.0;
+  const double se = (t.xr && t.yb) ? (double)sc[(size_t)(t.y0 + 1) * W + t.x0 + 1] : 0.0;
+  return (float)((1.0 - t.fy) * ((1.0 - t.fx) * nw + t.fx * ne) + t.fy * ((1.0 - t.fx) * sw + t.fx * se));
 }

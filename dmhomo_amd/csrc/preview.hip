@@ -135,37 +135,14 @@ __global__ __launch_bounds__(256) void homography_warp_kernel(const float* __res
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= Hd * Wd) return;
   const int yi = p / Wd, xi = p % Wd;
-  const double* m = Hm + (size_t)b * 9;
-  // adjugate / determinant
-  const double a0 = m[4] * m[8] - m[5] * m[7], a1 = m[2] * m[7] - m[1] * m[8], a2 = m[1] * m[5] - m[2] * m[4];
-  const double a3 = m[5] * m[6] - m[3] * m[8], a4 = m[0] * m[8] - m[2] * m[6], a5 = m[2] * m[3] - m[0] * m[5];
-  const double a6 = m[3] * m[7] - m[4] * m[6], a7 = m[1] * m[6] - m[0] * m[7], a8 = m[0] * m[4] - m[1] * m[3];
-  const double det = m[0] * a0 + m[1] * a3 + m[2] * a6;
-  const double id = det != 0.0 ? 1.0 / det : 0.0;      // (cv2.invert of a singular matrix gives zeros)
-  const double x = (double)xi, y = (double)yi;
-  const double qx = (a0 * id) * x + (a1 * id) * y + (a2 * id);
-  const double qy = (a3 * id) * x + (a4 * id) * y + (a5 * id);
-  const double qw = (a6 * id) * x + (a7 * id) * y + (a8 * id);
-  const double sx = qw != 0.0 ? qx / qw : 0.0, sy = qw != 0.0 ? qy / qw : 0.0;      // (cv2: w ? 1 / w : 0)
+  double inv[9];
+  double sx, sy;
+  homography_inverse(Hm + (size_t)b * 9, inv);      // geometry_dev.h: the three pieces are shared with relabel.hip
+  homography_warp_source(inv, xi, yi, sx, sy);
+  const HomographyWarpTaps t = homography_warp_taps(sx, sy, H, W);
   const size_t hw = (size_t)H * W, hwd = (size_t)Hd * Wd;
-  // every tap outside the image reads 0: a coordinate outside (-1, W) x (-1, H) (or NaN) has no tap inside
-  const bool any = sx > -1.0 && sx < (double)W && sy > -1.0 && sy < (double)H;
-  const double fx0 = floor(sx), fy0 = floor(sy);
-  const int x0 = any ? (int)fx0 : 0, y0 = any ? (int)fy0 : 0;      // -1 .. W-1, -1 .. H-1
-  const double fx = sx - fx0, fy = sy - fy0;
-  const bool xl = x0 >= 0, xr = x0 + 1 <= W - 1, yt = y0 >= 0, yb = y0 + 1 <= H - 1;
-  for (int c = 0; c < 3; ++c) {
-    float out = 0.f;
-    if (any) {
-      const float* sc = src + ((size_t)b * 3 + c) * hw;
-      const double nw = (xl && yt) ? (double)sc[(size_t)y0 * W + x0] : 0.0;
-      const double ne = (xr && yt) ? (double)sc[(size_t)y0 * W + x0 + 1] : 0.0;
-      const double sw = (xl && yb) ? (double)sc[(size_t)(y0 + 1) * W + x0] : 0.0;
-      const double se = (xr && yb) ? (double)sc[(size_t)(y0 + 1) * W + x0 + 1] : 0.0;
-      out = (float)((1.0 - fy) * ((1.0 - fx) * nw + fx * ne) + fy * ((1.0 - fx) * sw + fx * se));
-    }
-    dst[((size_t)b * 3 + c) * hwd + p] = out;
-  }
+  for (int c = 0; c < 3; ++c)
+    dst[((size_t)b * 3 + c) * hwd + p] = homography_warp_sample(src + ((size_t)b * 3 + c) * hw, t, W);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -433,6 +433,28 @@ def homo_gen(flow):
     return ops.dlt_homography(flow.to(torch.float32).contiguous()).reshape(-1, 1, 3, 3)
 
 
+RELABEL_BASES = ('identity', 'batch')
+
+
+def relabel_batch(data, sample_ids, seed=0, base='identity', ranges=ops.RELABEL_RANGES, fill=True, max_flow=256):
+    """A batch of real pairs under NEW homography labels, drawn on the device (dmh_relabel_batch, one launch; the definition:
+    include/dmhomo_hip_relabel.h; not in the reference).  data (B,12,H,W) [img1 | img2 | mask | rgb_flow | flow]; sample_ids (B,)
+    the GLOBAL sample indices (the label of a sample is a pure function of (seed, id, ranges, size), whatever the batch it
+    arrives in); base 'identity': the label is the drawn perturbation, SyntheticConditions' parameterisation with ``ranges`` =
+    (max_affine, max_shift, max_persp); 'batch': the perturbation applied on top of the batch's own homography,
+    ops.dlt_homography of its flow channels.  -> (data_new, homos (B,3,3) f64, valid (B,1,H,W) uint8): data_new keeps img1 and
+    the mask, carries the label's flow and flow image and, as img2, img1 warped by the label — where the warp has no source
+    pixel (valid == 0) the batch's own img2 with ``fill``, zeros without."""
+    if base not in RELABEL_BASES:
+        raise ValueError(f"relabel_batch: base = {base!r}: 'identity' or 'batch'")
+    ranges = ops.relabel_ranges(ranges)
+    data = data.to(torch.float32).contiguous()
+    ids = torch.as_tensor(sample_ids, dtype=torch.int64).to(data.device).contiguous()
+    hb = ops.dlt_homography(data[:, -2:].contiguous()) if base == 'batch' else None
+    out, homos, valid = ops.relabel_batch(data, ids, seed, ranges, max(max_flow, 1.), hb, fill)
+    return out, homos, valid.unsqueeze(1)
+
+
 def saveTrainPair(torch_tensor, mask, flows):
     """G6, DDP:1664-1678: {"imgs": uint8 (B,6,H,W), "homos": float64 (B,3,3)}."""
     assert torch.max(torch_tensor) <= 1, \
@@ -632,6 +654,13 @@ class Trainer(object):
     score_known = False
     last_known_error = None
     strength = None
+    relabel = None
+    relabel_ranges = ops.RELABEL_RANGES
+    relabel_seed = 0
+    relabel_first = 0
+    last_relabel_homos = None
+    last_relabel_valid = None
+    _relabel_seen = 0                     # rows relabelled by earlier calls
 
     def __init__(self, diffusion_model, folder, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_horizontal_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10,
@@ -775,6 +804,20 @@ class Trainer(object):
             if snap is not None:
                 rng.restore(snap, dev)
 
+    def _relabel(self, data, dev):
+        """the loader's (batch, classes, ...) with the batch replaced by relabel_batch of it, on ``dev``"""
+        batch = data[0].to(dev)
+        B = int(batch.shape[0])
+        rng = getattr(self.ema.ema_model, 'rng', None)
+        if isinstance(rng, DeviceRng) and rng.keyed:
+            ids = rng.ids_for(B)                             # the ids the noise uses, already on the device
+        else:
+            ids = torch.arange(B, dtype=torch.int64, device=dev) + (int(self.relabel_first) + self._relabel_seen)
+        new, homos, valid = relabel_batch(batch, ids, self.relabel_seed, self.relabel, self.relabel_ranges)
+        self._relabel_seen += B
+        self.last_relabel_homos, self.last_relabel_valid = homos, valid
+        return (new,) + tuple(data[1:])
+
     def sample(self, idx, rank, step=1):
         """DDP:1941-2021.  With ``preview`` set, every 100th ``step`` also writes the flow-remap and homography-warp sheets and
         their GIFs under generate_training_pairs/ (DDP:1972-2019); the record returned is the same either way."""
@@ -783,7 +826,16 @@ class Trainer(object):
         if dump and self.image_size != 256:
             raise ValueError(f'Trainer.sample with preview: the homography-warp sheet puts a (256, 256) canvas beside the '
                              f'record (DDP:1527), so it needs image_size 256, not {self.image_size}')
+        if self.relabel is not None:
+            if self.relabel not in RELABEL_BASES:
+                raise ValueError(f"Trainer.relabel = {self.relabel!r}: None, 'identity' or 'batch'")
+            if self.keep == 'target':
+                raise ValueError("Trainer.relabel with keep = 'target': the batch's target belongs to the old label; keep the "
+                                 "source (keep = 'source') or nothing")
+            ops.relabel_ranges(self.relabel_ranges)
         data = next(self.dl)
+        if self.relabel is not None:
+            data = self._relabel(data, dev)
         rgb_flows = data[0][:, -5:-2].to(dev)
         flows = data[0][:, -2:].to(dev).contiguous()
         mask = data[0][:, -6:-5].to(dev)

@@ -1056,6 +1056,50 @@ def start_mix(init01, ca, cb, *, noise=None, sample_ids=None, state=None, out=No
     return out
 
 
+RELABEL_RANGES = (.03, 8., 3e-5)          # (max_affine, max_shift, max_persp): the constants of ddpm.SyntheticConditions
+
+
+def relabel_ranges(ranges):
+    """(max_affine, max_shift, max_persp) as three floats, refused as include/dmhomo_hip_relabel.h says: negative or not finite,
+    max_affine >= 0.25, max_persp >= 5e-4"""
+    try:
+        a, t, p = (float(v) for v in ranges)
+    except (TypeError, ValueError):
+        raise ValueError(f'relabel ranges = {ranges!r}: three numbers (max_affine, max_shift, max_persp)') from None
+    if not all(math.isfinite(v) and v >= 0. for v in (a, t, p)):
+        raise ValueError(f'relabel ranges = {ranges!r}: each must be a finite number >= 0')
+    if a >= 0.25:
+        raise ValueError(f'relabel ranges: max_affine = {a!r} must be below 0.25 (the linear part stays diagonally dominant)')
+    if p >= 5e-4:
+        raise ValueError(f"relabel ranges: max_persp = {p!r} must be below 5e-4 (w' stays >= 0.5 inside the frame)")
+    return a, t, p
+
+
+def relabel_batch(data, sample_ids, seed=0, ranges=RELABEL_RANGES, max_flow=256., base=None, fill=True, out=None, homos=None,
+                  valid=None):
+    """a batch re-labelled in one launch (dmh_relabel_batch; the definition: include/dmhomo_hip_relabel.h): data (B,12,H,W) fp32
+    [img1 | img2 | mask | rgb_flow | flow], sample_ids (B,) int64 on the device, base (B,3,3) f64 or None -> (out (B,12,H,W),
+    homos (B,3,3) f64, valid (B,H,W) uint8): a new homography per sample id, its flow and flow image, img1 warped by it as the
+    target (the batch's img2 where the warp has no source pixel and ``fill``), img1 and mask copied."""
+    if data.dim() != 4 or data.shape[1] != 12:
+        raise ValueError(f'relabel_batch: data {tuple(data.shape)}: a (B, 12, H, W) batch expected')
+    B, _, H, W = (int(v) for v in data.shape)
+    a, t, p = relabel_ranges(ranges)
+    if tuple(sample_ids.shape) != (B,):
+        raise ValueError(f'relabel_batch: sample_ids {tuple(sample_ids.shape)}: {B} int64 (one per row) expected')
+    if base is not None and tuple(base.shape) != (B, 3, 3):
+        raise ValueError(f'relabel_batch: base {tuple(base.shape)}: ({B}, 3, 3) float64 expected')
+    out = torch.empty_like(data) if out is None else out
+    homos = torch.empty((B, 3, 3), device=data.device, dtype=torch.float64) if homos is None else homos
+    valid = torch.empty((B, H, W), device=data.device, dtype=torch.uint8) if valid is None else valid
+    if tuple(out.shape) != tuple(data.shape) or tuple(homos.shape) != (B, 3, 3) or tuple(valid.shape) != (B, H, W):
+        raise ValueError(f'relabel_batch: out {tuple(out.shape)} / homos {tuple(homos.shape)} / valid {tuple(valid.shape)} against '
+                         f'data {tuple(data.shape)}')
+    call('dmh_relabel_batch', ptr(data), ptr(sample_ids, torch.int64), int(seed) & 0xFFFFFFFFFFFFFFFF, a, t, p, float(max_flow),
+         ptr(base, torch.float64), int(bool(fill)), ptr(out), ptr(homos, torch.float64), ptr(valid, torch.uint8), B, H, W)
+    return out, homos, valid
+
+
 def rng_keep_mask(sample_ids, state, prob):
     """(B,) uint8: uniform draw of the indexed generator < prob (the class-dropout mask of CFG:84-90), one launch."""
     B = sample_ids.shape[0]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in counterpart of the reference's DGM/dgm_sample.py on dmhomo_amd (same CLI flags, same output format).
 
-    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3] [--keep source --known_resample 2] [--strength 0.5]
+    python scripts/dgm_sample.py -c DGM --s_step 32 --bs 25 --exp run0 [--image_size 256] [--batches 2] [--preview] [--sampler dpmpp_2m] [--clip_mode dynamic] [--guidance_rescale 0.7] [--guidance_interval 0.25 0.75] [--apg_eta 0 --apg_norm_threshold 15 --apg_momentum -0.5] [--photo_guidance 0.5] [--flow_guidance 2] [--pag_scale 3] [--keep source --known_resample 2] [--strength 0.5] [--relabel identity --relabel_seed 1 --relabel_ranges .03 8 3e-5]
 
 Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by what is available offline:
   * conditions come from dmhomo_amd.ddpm.SyntheticConditions (the CA-Homo dataset of DDP:1058-1066 is not
@@ -51,6 +51,17 @@ Differences from the reference script (DGM/dgm_sample.py:11-101), all forced by 
     batch's.  With SyntheticConditions, whose image channels are zeros, the start is a noised black pair: the flag is meant for
     --conditions / a dataset folder.  A strength below 1 / s_step runs no entry and is refused; the default, off, is the
     reference's sampler;
+  * --relabel identity|batch replaces every batch, directly behind the loader, by the same real source images under NEW homography
+    labels drawn on the device (dmhomo_amd.ddpm.relabel_batch, one launch; an addition): per sample a perturbation in
+    SyntheticConditions' parameterisation — --relabel_ranges A T P bound its affine entries, its shift in pixels of the 360 x 640
+    frame and its perspective entries, default .03 8 3e-5 — taken as the label itself (identity) or applied on top of the batch's
+    own homography (batch), with its flow and flow image, and the source warped by it in place of the batch's target.  The draw
+    is keyed by --relabel_seed (default: --seed) and the global sample index, like the noise, so a job's labels do not depend on
+    the number of ranks.  With --keep source --strength F the record holds the real source and a target generated under the
+    fresh label, started from the warped source, at F times the UNet passes: finite real scenes yield unlimited labels.  Not
+    together with --keep target (the batch's target belongs to the old label).  With SyntheticConditions, whose image channels
+    are zeros, the images are black: the flag is meant for --conditions / a dataset folder.  Sample quality with trained weights:
+    not measured.  The default, off, leaves every batch as the loader dealt it;
   * --preview turns on the flow-remap and homography-warp sheets the reference always writes under
     generate_training_pairs/ when its step counter is a multiple of 100 (DDP:1972-2019); off by default;
   * multi-GPU: launch with torch.distributed.run instead of N hand-started processes (--gpu_nums / -i are
@@ -133,6 +144,15 @@ parser.add_argument('--strength', type=float, default=None,
                     help="start every batch from its own pair noised to an intermediate time and run the last floor(s_step * "
                          "STRENGTH) entries only, STRENGTH in (0, 1] (SDEdit; not in the reference; GaussianDiffusion.sample_from, "
                          "Trainer.strength); default: off")
+parser.add_argument('--relabel', choices=('identity', 'batch'), default=None,
+                    help="draw a new homography label per sample on the device and sample every batch under it: the label is the "
+                         "drawn perturbation (identity) or the perturbation on top of the batch's own homography (batch); meant "
+                         "for --conditions / a dataset folder — with SyntheticConditions the images are black (not in the "
+                         "reference; ddpm.relabel_batch, Trainer.relabel); default: off")
+parser.add_argument('--relabel_seed', type=int, default=None, help='with --relabel: seed of the label draw; default: --seed')
+parser.add_argument('--relabel_ranges', type=float, nargs=3, default=None, metavar=('A', 'T', 'P'),
+                    help='with --relabel: bounds of the affine entries (< 0.25), the shift in pixels of the 360 x 640 frame and the '
+                         'perspective entries (< 5e-4) of the drawn perturbation; default: .03 8 3e-5')
 args = parser.parse_args()
 
 num_classes = 1
@@ -176,6 +196,10 @@ def main():
     trainer.keep, sampler.known_resample = args.keep, args.known_resample
     trainer.score_known = args.keep is not None
     trainer.strength = args.strength
+    trainer.relabel = args.relabel
+    trainer.relabel_seed = args.seed if args.relabel_seed is None else args.relabel_seed
+    if args.relabel_ranges is not None:
+        trainer.relabel_ranges = tuple(args.relabel_ranges)
     sampler.model.dedup_dropped_rows = True                # CFG:404,415-425: dropped conditional rows == null rows, not computed
     out_dir = f'traindata/{args.exp}/dataset/'
     os.makedirs(out_dir, exist_ok=True)
